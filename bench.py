@@ -12,6 +12,11 @@ source batches fully processed through the engine (big polls amortize
 per-step engine overhead and keep the default timed region >= ~5 s).
 
 Run: python bench.py [--gpus N] [--steps K] [--warmup W]
+         [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times K steps and prints one JSON result
+line.  `--dump-outputs DIR` also writes what the last timed step
+emitted (see `dump_outputs`); `--full` adds the measurements that take
+runs of their own (native-engine latency probes).
 Multi-GPU: python -m torch.distributed.run --nnodes=1 --nproc-per-node N
            --master-addr 127.0.0.1 bench.py --gpus N ...
 """
@@ -77,7 +82,20 @@ def parse_args():
         type=int,
         default=20,
         help="extra synced single-step runs after the timed region to "
-        "measure per-step latency (native engine)",
+        "measure per-step latency (native engine; only with --full)",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the measurements the headline figure does not "
+        "need (the native engine's isolated latency probes)",
+    )
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write the closed-window rows the "
+        "last timed step emitted as DIR/<name>.npy (float64)",
     )
     p.add_argument(
         "--engine",
@@ -89,6 +107,88 @@ def parse_args():
         "(kernel-pipeline comparison, single-GPU only)",
     )
     return p.parse_args()
+
+
+# --dump-outputs budget: 3 float64 columns x 2M rows = 48 MB (< 64 MB).
+DUMP_MAX_ROWS = 2_000_000
+
+
+def dump_outputs(dirpath, batches, suffix=""):
+    """Write the closed-window rows in `batches` (RecordBatches as the
+    sink received them) as ``keys``, ``window_start_ms`` and ``counts``
+    ``.npy`` columns (float64; exact, all values < 2^53), plus the
+    total row count in ``n_rows``.
+
+    The close kernels append rows in atomic-arrival order, so rows are
+    first put in canonical (window start, key) order; each (key, window)
+    cell is emitted once, so that order is total.  Above DUMP_MAX_ROWS a
+    fixed seeded sample of the ordered rows is written instead (the
+    sampled positions depend on the row count alone).
+    """
+    import numpy as np
+    import torch
+
+    os.makedirs(dirpath, exist_ok=True)
+    if batches:
+        keys = torch.cat([b.keys for b in batches]).to(torch.int64)
+        ts = torch.cat([b.ts for b in batches]).to(torch.int64)
+        vals = torch.cat([b.vals for b in batches]).to(torch.int64)
+        order = torch.argsort(keys, stable=True)
+        order = order[torch.argsort(ts[order], stable=True)]
+        n = int(order.numel())
+        if n > DUMP_MAX_ROWS:
+            pick = np.sort(
+                np.random.default_rng(0).choice(
+                    n, DUMP_MAX_ROWS, replace=False
+                )
+            )
+            order = order[torch.from_numpy(pick).to(order.device)]
+        cols = [c[order].cpu().numpy() for c in (keys, ts, vals)]
+    else:
+        n = 0
+        cols = [np.zeros(0, dtype=np.int64)] * 3
+    names = ("keys", "window_start_ms", "counts")
+    for name, col in zip(names, cols):
+        np.save(
+            os.path.join(dirpath, f"{name}{suffix}.npy"),
+            col.astype(np.float64),
+        )
+    np.save(
+        os.path.join(dirpath, f"n_rows{suffix}.npy"),
+        np.array([n], dtype=np.float64),
+    )
+
+
+def preload_extension():
+    """Hand the package the kernel library that build() compiled.
+
+    Package versions whose loader always goes through the JIT builder
+    need write access to the build directory (for its lock file) even
+    when the build is up to date, so they cannot be timed from a tree
+    that is read-only to the benchmark's user.  For those, import the
+    built library directly, as the current loader does itself; a
+    missing or stale library is left to the package's own loader, which
+    builds it or fails loudly.
+    """
+    import importlib.util
+
+    import torch  # noqa: F401  (the library links against libtorch)
+    from bytewax_amd.gpu import _ext as ext_mod
+
+    if ext_mod._ext is not None or hasattr(ext_mod, "load_built"):
+        return
+    name = "bytewax_amd_stream_kernels"
+    so = ext_mod._BUILD_DIR / f"{name}.so"
+    try:
+        built = so.stat().st_mtime
+        if any(s.stat().st_mtime > built for s in ext_mod._SOURCES):
+            return
+    except OSError:
+        return
+    spec = importlib.util.spec_from_file_location(name, str(so))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    ext_mod._ext = mod
 
 
 def main():
@@ -122,6 +222,9 @@ def main():
     from bytewax_amd.inputs import DynamicSource
     from bytewax_amd.testing import run_main
 
+    if on_gpu:
+        preload_extension()
+
     align = datetime(2024, 1, 1, tzinfo=timezone.utc)
     K, W = args.steps, args.warmup
     E = args.events_per_batch
@@ -135,7 +238,13 @@ def main():
                 torch.cuda.synchronize()
 
     B = args.batches_per_poll
-    timings = {"t0": None, "t1": None, "step_starts": []}
+    timings = {
+        "t0": None,
+        "t1": None,
+        "step_starts": [],
+        "last_step_from": 0,
+        "last_step_to": 0,
+    }
 
     class _BenchPartition(_SyntheticPartition):
         """Source partition with timing hooks: polls are the step
@@ -152,9 +261,14 @@ def main():
                 timings["t0"] = time.perf_counter()
             if W <= i <= W + K:
                 timings["step_starts"].append(time.perf_counter())
+            if i == W + K - 1:
+                # Everything the sink holds so far predates the last
+                # timed step (--dump-outputs writes what follows).
+                timings["last_step_from"] = len(out)
             if i == W + K:
                 barrier_sync()
                 timings["t1"] = time.perf_counter()
+                timings["last_step_to"] = len(out)
                 raise StopIteration()
             return super().next_batch()
 
@@ -237,10 +351,16 @@ def main():
         barrier_sync()
         t1 = time.perf_counter()
         timings["t0"], timings["t1"] = t0, t1
+        if args.dump_outputs:
+            # The native loop hands its caller row counts only; the
+            # rows of its latest window close stay in the state's out
+            # staging buffers (rewritten by every close).
+            last = state._read_out()
+            last_step_out = [last] if last is not None else []
         # Latency probes: single batches with a sync each, after the
         # throughput region (launch-to-launch gaps are not a latency
         # measure under async execution).
-        for i in range(args.latency_probes):
+        for i in range(args.latency_probes if args.full else 0):
             lt0 = time.perf_counter()
             r, _ = run_steps((W + K) * B + i, 1)
             closed_rows += r
@@ -276,6 +396,16 @@ def main():
             (b - a) * 1000.0 for a, b in zip(steps[:-1], steps[1:])
         )
         closed_rows = sum(len(b) for b in out)
+        last_step_out = out[
+            timings["last_step_from"] : timings["last_step_to"]
+        ]
+
+    if args.dump_outputs:
+        dump_outputs(
+            args.dump_outputs,
+            last_step_out,
+            suffix=f"_rank{rank}" if world > 1 else "",
+        )
 
     elapsed = timings["t1"] - timings["t0"]
     # Max over ranks.
@@ -329,11 +459,13 @@ def main():
                         # engine reports steady-state poll-gap deltas
                         # (latency under load); the native loop runs
                         # isolated synced single-batch probes after
-                        # the throughput region.
+                        # the throughput region, with --full only.
                         "latency_method": (
                             "poll-gap under load"
                             if engine == "python"
                             else "isolated synced single-step probes"
+                            if args.full
+                            else "not measured (needs --full)"
                         ),
                         "closed_window_rows": closed_rows,
                     },

@@ -33,12 +33,41 @@ def build(verbose: bool = False):
     )
 
 
+_NAME = "bytewax_amd_stream_kernels"
+
+
+def load_built():
+    """Import the already-built ``.so`` if it is no older than its
+    sources; None otherwise.
+
+    The JIT loader takes a lock file in the build directory even when
+    nothing needs compiling, so it cannot run for a user to whom the
+    tree is read-only (a shared checkout, an installed package); a
+    plain import can.
+    """
+    import importlib.util
+
+    so = _BUILD_DIR / f"{_NAME}.so"
+    try:
+        built = so.stat().st_mtime
+        if any(s.stat().st_mtime > built for s in _SOURCES):
+            return None
+    except OSError:
+        return None
+    import torch  # noqa: F401  (the .so links against libtorch)
+
+    spec = importlib.util.spec_from_file_location(_NAME, str(so))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def ext():
     """Load (building if necessary) the kernel extension."""
     global _ext
     if _ext is None:
         try:
-            _ext = build()
+            _ext = load_built() or build()
         except Exception as ex:
             import torch
 
