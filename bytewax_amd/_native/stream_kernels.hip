@@ -2060,6 +2060,301 @@ __global__ void k_session_close_migrate(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Out-of-order session windows: up to `max_open` open sessions per
+// key.  Table layout: skeys[nslots], scnt[nslots] (open sessions in
+// the cell) and start/last/acc of shape [nslots, max_open], sessions
+// sorted by start inside a cell and separated by more than the gap.
+//
+// An insert is three launches over the (key, ts)-sorted batch:
+//   k_session_run_count    per-block count of run heads
+//   k_session_run_collapse one (key, start, last, acc) record per run
+//   k_session_run_merge    two-pointer merge of a key's runs into its
+//                          cell, coalescing across the gap
+// The first two are parallel over events, the third over runs; insert
+// never closes a session (an event may still bridge two of them), so
+// only k_session_multi_close_migrate emits.
+
+#define SESS_RUN_BLK 256
+#define SESS_ERR_TABLE 1
+#define SESS_ERR_MAX_OPEN 2
+
+// Event i starts a run iff it is the first event, the first of its
+// key, or more than the gap after its predecessor.
+__device__ inline bool session_run_head(
+    const int32_t* __restrict__ keys, const int64_t* __restrict__ ts,
+    int64_t i, int64_t gap_ms) {
+  if (i == 0) return true;
+  if (keys[i] != keys[i - 1]) return true;
+  return ts[i] - ts[i - 1] > gap_ms;
+}
+
+__global__ __launch_bounds__(SESS_RUN_BLK) void k_session_run_count(
+    const int32_t* __restrict__ keys,  // sorted by (key, ts)
+    const int64_t* __restrict__ ts,
+    int64_t n,
+    int64_t gap_ms,
+    int* __restrict__ block_heads) {
+  __shared__ int wave_cnt[SESS_RUN_BLK / WAVE];
+  int64_t i = blockIdx.x * (int64_t)SESS_RUN_BLK + threadIdx.x;
+  int lane = threadIdx.x & (WAVE - 1);
+  int wave = threadIdx.x / WAVE;
+  bool head = i < n && session_run_head(keys, ts, i, gap_ms);
+  unsigned long long ball = __ballot(head);
+  if (lane == 0) wave_cnt[wave] = __popcll(ball);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int total = 0;
+    for (int w = 0; w < SESS_RUN_BLK / WAVE; ++w) total += wave_cnt[w];
+    block_heads[blockIdx.x] = total;
+  }
+}
+
+// Pass B: recompute the head flags, rank them (ballot/popcount inside
+// the wave, LDS offsets across waves, `block_off` across blocks) and
+// write one record per run in sorted order.  Every event knows its
+// run id (heads at or before it, minus one), so no thread loops over
+// a run: heads write key/start, tails write last, and the accumulator
+// is tail index minus head index (COUNT) or a wave-level segmented
+// shuffle reduction with one int64 atomicAdd per (wave, run) (SUM —
+// integer adds, so exact and order-independent).  `run_acc` arrives
+// zeroed.
+template <int MODE>
+__global__ __launch_bounds__(SESS_RUN_BLK) void k_session_run_collapse(
+    const int32_t* __restrict__ keys,
+    const int64_t* __restrict__ ts,
+    const int64_t* __restrict__ vals,
+    int64_t n,
+    int64_t gap_ms,
+    const int64_t* __restrict__ block_off,  // exclusive scan of heads
+    int32_t* __restrict__ run_key,
+    long long* __restrict__ run_start,
+    long long* __restrict__ run_last,
+    unsigned long long* __restrict__ run_acc) {
+  __shared__ int wave_cnt[SESS_RUN_BLK / WAVE];
+  int64_t i = blockIdx.x * (int64_t)SESS_RUN_BLK + threadIdx.x;
+  int lane = threadIdx.x & (WAVE - 1);
+  int wave = threadIdx.x / WAVE;
+  bool in = i < n;
+  bool head = in && session_run_head(keys, ts, i, gap_ms);
+  unsigned long long ball = __ballot(head);
+  if (lane == 0) wave_cnt[wave] = __popcll(ball);
+  __syncthreads();
+  int before = 0;
+  for (int w = 0; w < wave; ++w) before += wave_cnt[w];
+  unsigned long long le =
+      lane == WAVE - 1 ? ~0ULL : ((1ULL << (lane + 1)) - 1ULL);
+  // Event 0 is a head, so every in-range event has rid >= 0.
+  int64_t rid =
+      in ? block_off[blockIdx.x] + before + __popcll(ball & le) - 1 : -1;
+  bool tail = false;
+  if (in) {
+    tail = i == n - 1 || keys[i + 1] != keys[i] ||
+           ts[i + 1] - ts[i] > gap_ms;
+    if (head) {
+      run_key[rid] = keys[i];
+      run_start[rid] = ts[i];
+    }
+    if (tail) run_last[rid] = ts[i];
+  }
+  if (MODE == AGG_COUNT) {
+    long long d = (tail ? i + 1 : 0) - (head ? i : 0);
+    if (d != 0) atomicAdd(&run_acc[rid], (unsigned long long)d);
+  } else {
+    long long v = in ? vals[i] : 0;
+    // rid is non-decreasing across the wave: a segmented suffix sum.
+    for (int off = 1; off < WAVE; off <<= 1) {
+      long long ov = __shfl_down(v, off);
+      long long orid = __shfl_down((long long)rid, off);
+      if (lane + off < WAVE && orid == rid) v += ov;
+    }
+    long long prid = __shfl_up((long long)rid, 1);
+    if (in && (lane == 0 || prid != rid)) {
+      atomicAdd(&run_acc[rid], (unsigned long long)v);
+    }
+  }
+}
+
+// One thread per run; only the first run of a key acts, and takes the
+// key's following runs with it, so one thread owns a key (and, after
+// the CAS claim, its cell) for the whole launch.  The merged list is
+// staged in LDS ([session][thread], conflict-free) rather than in
+// private arrays.  More than MAX_OPEN sessions raise the flag and
+// leave the cell as it was.
+template <int MAX_OPEN>
+__global__ __launch_bounds__(WAVE) void k_session_run_merge(
+    const int32_t* __restrict__ run_key,
+    const long long* __restrict__ run_start,
+    const long long* __restrict__ run_last,
+    const long long* __restrict__ run_acc,
+    const int64_t* __restrict__ n_runs_p,
+    int64_t run_cap,
+    int64_t gap_ms,
+    uint64_t* __restrict__ skeys,
+    int* __restrict__ scnt,
+    long long* __restrict__ sstart,
+    long long* __restrict__ slast,
+    long long* __restrict__ sacc,
+    uint64_t mask,
+    unsigned long long* __restrict__ max_ts,
+    int* __restrict__ error_flag) {
+  __shared__ long long l_start[MAX_OPEN][WAVE];
+  __shared__ long long l_last[MAX_OPEN][WAVE];
+  __shared__ long long l_acc[MAX_OPEN][WAVE];
+  int tid = threadIdx.x;
+  int64_t n_runs = *n_runs_p;
+  if (n_runs > run_cap) n_runs = run_cap;
+  int64_t stride = gridDim.x * (int64_t)WAVE;
+  long long mx = 0;
+  for (int64_t r = blockIdx.x * (int64_t)WAVE + tid; r < n_runs;
+       r += stride) {
+    long long rl = run_last[r];
+    if (rl > mx) mx = rl;
+    int32_t k = run_key[r];
+    if (r > 0 && run_key[r - 1] == k) continue;
+    uint64_t slot =
+        session_find_or_claim(skeys, mask, (uint64_t)(uint32_t)k);
+    if (slot == ~0ULL) {
+      atomicOr(error_flag, SESS_ERR_TABLE);
+      continue;
+    }
+    int c = scnt[slot];
+    if (c > MAX_OPEN) c = MAX_OPEN;
+    long long* cs = sstart + slot * MAX_OPEN;
+    long long* cl = slast + slot * MAX_OPEN;
+    long long* ca = sacc + slot * MAX_OPEN;
+    int a = 0;
+    int64_t b = r;
+    int m = 0;
+    bool have = false;
+    long long cur_s = 0, cur_l = 0, cur_a = 0;
+    while (true) {
+      bool ha = a < c;
+      bool hb = b < n_runs && run_key[b] == k;
+      if (!ha && !hb) break;
+      long long ns, nl, na;
+      if (ha && (!hb || cs[a] <= run_start[b])) {
+        ns = cs[a];
+        nl = cl[a];
+        na = ca[a];
+        ++a;
+      } else {
+        ns = run_start[b];
+        nl = run_last[b];
+        na = run_acc[b];
+        ++b;
+      }
+      if (have && ns - cur_l <= gap_ms) {
+        if (nl > cur_l) cur_l = nl;
+        cur_a += na;
+      } else {
+        if (have) {
+          if (m < MAX_OPEN) {
+            l_start[m][tid] = cur_s;
+            l_last[m][tid] = cur_l;
+            l_acc[m][tid] = cur_a;
+          }
+          ++m;
+        }
+        cur_s = ns;
+        cur_l = nl;
+        cur_a = na;
+        have = true;
+      }
+    }
+    if (have) {
+      if (m < MAX_OPEN) {
+        l_start[m][tid] = cur_s;
+        l_last[m][tid] = cur_l;
+        l_acc[m][tid] = cur_a;
+      }
+      ++m;
+    }
+    if (m > MAX_OPEN) {
+      atomicOr(error_flag, SESS_ERR_MAX_OPEN);
+      continue;
+    }
+    for (int j = 0; j < m; ++j) {
+      cs[j] = l_start[j][tid];
+      cl[j] = l_last[j][tid];
+      ca[j] = l_acc[j][tid];
+    }
+    scnt[slot] = m;
+  }
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    long long other = __shfl_down(mx, off);
+    if (other > mx) mx = other;
+  }
+  if (tid == 0 && mx > 0) atomicMax(max_ts, (unsigned long long)mx);
+}
+
+// Per slot: sessions in a cell are sorted and gap-separated, so the
+// closable ones (last < horizon) form a prefix.  Emit the prefix,
+// compact the rest to the front of the key's cell in the alternate
+// table.
+__global__ void k_session_multi_close_migrate(
+    const uint64_t* __restrict__ skeys,
+    const int* __restrict__ scnt,
+    const long long* __restrict__ sstart,
+    const long long* __restrict__ slast,
+    const long long* __restrict__ sacc,
+    int64_t nslots,
+    int max_open,
+    int64_t horizon_ms,
+    uint64_t* __restrict__ dst_keys,
+    int* __restrict__ dst_cnt,
+    long long* __restrict__ dst_start,
+    long long* __restrict__ dst_last,
+    long long* __restrict__ dst_acc,
+    uint64_t mask,
+    int32_t* __restrict__ out_keys,
+    int64_t* __restrict__ out_start,
+    int64_t* __restrict__ out_end,
+    int64_t* __restrict__ out_vals,
+    int* __restrict__ out_n,
+    int64_t out_cap,
+    int* __restrict__ error_flag) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (; i < nslots; i += stride) {
+    uint64_t key = skeys[i];
+    if (key == EMPTY_SLOT) continue;
+    int c = scnt[i];
+    if (c > max_open) c = max_open;
+    if (c <= 0) continue;
+    int64_t base = i * max_open;
+    int p = 0;
+    while (p < c && slast[base + p] < horizon_ms) ++p;
+    if (p > 0) {
+      int idx = atomicAdd(out_n, p);
+      for (int j = 0; j < p; ++j) {
+        if ((int64_t)idx + j < out_cap) {
+          out_keys[idx + j] = (int32_t)(uint32_t)key;
+          out_start[idx + j] = sstart[base + j];
+          out_end[idx + j] = slast[base + j];
+          out_vals[idx + j] = sacc[base + j];
+        } else {
+          atomicOr(error_flag, SESS_ERR_TABLE);
+        }
+      }
+    }
+    if (p < c) {
+      uint64_t slot = session_find_or_claim(dst_keys, mask, key);
+      if (slot == ~0ULL) {
+        atomicOr(error_flag, SESS_ERR_TABLE);
+        continue;
+      }
+      int64_t dbase = (int64_t)slot * max_open;
+      for (int j = p; j < c; ++j) {
+        dst_start[dbase + j - p] = sstart[base + j];
+        dst_last[dbase + j - p] = slast[base + j];
+        dst_acc[dbase + j - p] = sacc[base + j];
+      }
+      dst_cnt[slot] = c - p;
+    }
+  }
+}
+
 // Stream compaction: keep events where mask != 0, preserving relative
 // order per wave (wave-ballot ranks + one atomic per wave).
 __global__ void k_filter_compact(
@@ -3942,6 +4237,176 @@ void session_restore(
       (uint64_t)(nslots - 1), error_flag.data_ptr<int32_t>());
 }
 
+// Collapse a (key, ts)-sorted batch into runs.  Returns
+// {run_key, run_start, run_last, run_acc, n_runs}; the run columns
+// are sized for the worst case (one run per event) and `n_runs` stays
+// on the device, so the call never synchronises.
+std::vector<torch::Tensor> session_run_collapse(
+    torch::Tensor keys,  // SORTED by (key, ts)
+    torch::Tensor ts,
+    c10::optional<torch::Tensor> vals,
+    int64_t gap_ms,
+    int64_t mode) {
+  check_dev(keys, torch::kInt32, "keys");
+  check_dev(ts, torch::kInt64, "ts");
+  int64_t n = keys.numel();
+  TORCH_CHECK(n > 0, "session_run_collapse needs a non-empty batch");
+  TORCH_CHECK(ts.numel() == n, "keys/ts length mismatch");
+  TORCH_CHECK(gap_ms >= 0, "gap must not be negative");
+  TORCH_CHECK(mode == AGG_COUNT || mode == AGG_SUM, "count or sum only");
+  const int64_t* vals_p = nullptr;
+  if (mode == AGG_SUM) {
+    TORCH_CHECK(vals.has_value(), "sum sessions need a vals column");
+    check_dev(*vals, torch::kInt64, "vals");
+    TORCH_CHECK(vals->numel() == n, "keys/vals length mismatch");
+    vals_p = vals->data_ptr<int64_t>();
+  }
+  int64_t nblk = (n + SESS_RUN_BLK - 1) / SESS_RUN_BLK;
+  TORCH_CHECK(nblk < (1LL << 31), "batch too large");
+  auto i32 = keys.options().dtype(torch::kInt32);
+  auto i64 = keys.options().dtype(torch::kInt64);
+  auto block_heads = torch::empty({nblk}, i32);
+  auto stream = at::hip::getCurrentHIPStream();
+  dim3 grid((unsigned)nblk), block(SESS_RUN_BLK);
+  hipLaunchKernelGGL(
+      k_session_run_count, grid, block, 0, stream,
+      keys.data_ptr<int32_t>(), ts.data_ptr<int64_t>(), n, gap_ms,
+      block_heads.data_ptr<int32_t>());
+  auto incl = block_heads.cumsum(0, torch::kInt64);
+  auto block_off = incl - block_heads;
+  auto n_runs = incl.slice(0, nblk - 1, nblk).contiguous();
+  auto run_key = torch::empty({n}, i32);
+  auto run_start = torch::empty({n}, i64);
+  auto run_last = torch::empty({n}, i64);
+  auto run_acc = torch::zeros({n}, i64);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(
+        kern, grid, block, 0, stream, keys.data_ptr<int32_t>(),
+        ts.data_ptr<int64_t>(), vals_p, n, gap_ms,
+        block_off.data_ptr<int64_t>(), run_key.data_ptr<int32_t>(),
+        (long long*)run_start.data_ptr<int64_t>(),
+        (long long*)run_last.data_ptr<int64_t>(),
+        (unsigned long long*)run_acc.data_ptr<int64_t>());
+  };
+  if (mode == AGG_COUNT) launch(k_session_run_collapse<AGG_COUNT>);
+  else launch(k_session_run_collapse<AGG_SUM>);
+  return {run_key, run_start, run_last, run_acc, n_runs};
+}
+
+// Merge runs (sorted by (key, start), gap-separated per key) into the
+// multi-session table.  Also the restore path: snapshot rows are runs.
+void session_run_merge(
+    torch::Tensor run_key,
+    torch::Tensor run_start,
+    torch::Tensor run_last,
+    torch::Tensor run_acc,
+    torch::Tensor n_runs,
+    torch::Tensor skeys,
+    torch::Tensor scnt,
+    torch::Tensor sstart,
+    torch::Tensor slast,
+    torch::Tensor sacc,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    int64_t gap_ms,
+    int64_t max_open) {
+  check_dev(run_key, torch::kInt32, "run_key");
+  check_dev(run_start, torch::kInt64, "run_start");
+  check_dev(run_last, torch::kInt64, "run_last");
+  check_dev(run_acc, torch::kInt64, "run_acc");
+  check_dev(n_runs, torch::kInt64, "n_runs");
+  check_dev(scnt, torch::kInt32, "scnt");
+  int64_t cap = run_key.numel();
+  if (cap == 0) return;
+  TORCH_CHECK(run_start.numel() >= cap && run_last.numel() >= cap &&
+                  run_acc.numel() >= cap && n_runs.numel() == 1,
+              "run columns shorter than run_key");
+  int64_t nslots = skeys.numel();
+  TORCH_CHECK((nslots & (nslots - 1)) == 0, "table size must be 2^k");
+  TORCH_CHECK(scnt.numel() == nslots &&
+                  sstart.numel() == nslots * max_open &&
+                  slast.numel() == nslots * max_open &&
+                  sacc.numel() == nslots * max_open,
+              "session table shape does not match max_open");
+  auto stream = at::hip::getCurrentHIPStream();
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(
+        kern, dim3(n_blocks(cap, WAVE)), dim3(WAVE), 0, stream,
+        run_key.data_ptr<int32_t>(),
+        (const long long*)run_start.data_ptr<int64_t>(),
+        (const long long*)run_last.data_ptr<int64_t>(),
+        (const long long*)run_acc.data_ptr<int64_t>(),
+        n_runs.data_ptr<int64_t>(), cap, gap_ms,
+        (uint64_t*)skeys.data_ptr<int64_t>(), scnt.data_ptr<int32_t>(),
+        (long long*)sstart.data_ptr<int64_t>(),
+        (long long*)slast.data_ptr<int64_t>(),
+        (long long*)sacc.data_ptr<int64_t>(), (uint64_t)(nslots - 1),
+        (unsigned long long*)max_ts.data_ptr<int64_t>(),
+        error_flag.data_ptr<int32_t>());
+  };
+  switch (max_open) {
+    case 4: launch(k_session_run_merge<4>); break;
+    case 8: launch(k_session_run_merge<8>); break;
+    case 16: launch(k_session_run_merge<16>); break;
+    case 32: launch(k_session_run_merge<32>); break;
+    default: TORCH_CHECK(false, "max_open must be 4, 8, 16 or 32");
+  }
+}
+
+void session_multi_close_migrate(
+    torch::Tensor skeys,
+    torch::Tensor scnt,
+    torch::Tensor sstart,
+    torch::Tensor slast,
+    torch::Tensor sacc,
+    torch::Tensor dst_keys,
+    torch::Tensor dst_cnt,
+    torch::Tensor dst_start,
+    torch::Tensor dst_last,
+    torch::Tensor dst_acc,
+    torch::Tensor out_keys,
+    torch::Tensor out_start,
+    torch::Tensor out_end,
+    torch::Tensor out_vals,
+    torch::Tensor out_n,
+    torch::Tensor error_flag,
+    int64_t horizon_ms,
+    int64_t max_open) {
+  check_dev(scnt, torch::kInt32, "scnt");
+  check_dev(dst_cnt, torch::kInt32, "dst_cnt");
+  int64_t nslots = skeys.numel();
+  TORCH_CHECK((nslots & (nslots - 1)) == 0, "table size must be 2^k");
+  TORCH_CHECK(max_open >= 1 && max_open <= 32, "bad max_open");
+  TORCH_CHECK(dst_keys.numel() == nslots && scnt.numel() == nslots &&
+                  dst_cnt.numel() == nslots,
+              "session tables differ in size");
+  for (const auto& t : {sstart, slast, sacc, dst_start, dst_last, dst_acc}) {
+    TORCH_CHECK(t.numel() == nslots * max_open,
+                "session table shape does not match max_open");
+  }
+  int64_t out_cap = out_keys.numel();
+  TORCH_CHECK(out_start.numel() >= out_cap && out_end.numel() >= out_cap &&
+                  out_vals.numel() >= out_cap,
+              "out columns shorter than out_keys");
+  auto stream = at::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(
+      k_session_multi_close_migrate, dim3(n_blocks(nslots, 256)),
+      dim3(256), 0, stream, (const uint64_t*)skeys.data_ptr<int64_t>(),
+      scnt.data_ptr<int32_t>(),
+      (const long long*)sstart.data_ptr<int64_t>(),
+      (const long long*)slast.data_ptr<int64_t>(),
+      (const long long*)sacc.data_ptr<int64_t>(), nslots, (int)max_open,
+      horizon_ms, (uint64_t*)dst_keys.data_ptr<int64_t>(),
+      dst_cnt.data_ptr<int32_t>(),
+      (long long*)dst_start.data_ptr<int64_t>(),
+      (long long*)dst_last.data_ptr<int64_t>(),
+      (long long*)dst_acc.data_ptr<int64_t>(), (uint64_t)(nslots - 1),
+      out_keys.data_ptr<int32_t>(), out_start.data_ptr<int64_t>(),
+      out_end.data_ptr<int64_t>(), out_vals.data_ptr<int64_t>(),
+      out_n.data_ptr<int32_t>(), out_cap,
+      error_flag.data_ptr<int32_t>());
+}
+
 void join_extract(
     torch::Tensor tkeys,
     torch::Tensor tval0,
@@ -4860,6 +5325,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Emit sessions idle past the horizon; migrate live cells");
   m.def("session_restore", &session_restore,
         "Rebuild session cells from a host spill");
+  m.def("session_run_collapse", &session_run_collapse,
+        "Collapse a (key, ts)-sorted batch into gap-separated runs");
+  m.def("session_run_merge", &session_run_merge,
+        "Merge sorted runs into the multi-session table (also restore)");
+  m.def("session_multi_close_migrate", &session_multi_close_migrate,
+        "Emit each cell's closable prefix; migrate the open sessions");
   m.def("session_merge_batch", &session_merge_batch,
         "Merge per-key per-batch (count, min_ts, max_ts) rows into "
         "the session table (gap >= batch span fast path)");

@@ -1206,6 +1206,23 @@ class CollectCountsSink(DynamicSink[RecordBatch]):
         return _CollectCountsPartition(self._ls)
 
 
+def _concat_late(lates: List[RecordBatch]) -> Optional[RecordBatch]:
+    """One late RecordBatch per step (absolute timestamps when several
+    batches, possibly of different `ts_base`, contributed)."""
+    import torch
+
+    if not lates:
+        return None
+    if len(lates) == 1:
+        return lates[0]
+    with_vals = all(b.vals is not None for b in lates)
+    return RecordBatch(
+        torch.cat([b.keys for b in lates]),
+        torch.cat([b.ts.to(torch.int64) + b.ts_base for b in lates]),
+        torch.cat([b.vals for b in lates]) if with_vals else None,
+    )
+
+
 class _DeviceSessionLogic(StatefulBatchLogic):
     """Holds the HBM session table (gap-based windows)."""
 
@@ -1218,17 +1235,43 @@ class _DeviceSessionLogic(StatefulBatchLogic):
 
     def on_batch(self, batches):
         out = []
+        lates = []
         for batch in batches:
             if self.exchange:
                 batch = exchange_by_key(batch)
-            self.state.insert(batch)
+            late = self.state.insert(batch)
+            if late is not None:
+                lates.append(late)
         closed = self.state.close_due(self.wait_ms)
+        if not self.state.ordered:
+            closed = self._with_late(closed, lates)
         if closed is not None:
             out.append(closed)
         return (out, StatefulBatchLogic.RETAIN)
 
+    def _with_late(self, closed, lates):
+        """Unordered emissions carry a fifth entry, `late`: a step
+        with late events but no closed session still emits, with
+        empty columns."""
+        import torch
+
+        if closed is None and not lates:
+            return None
+        if closed is None:
+            dev = self.state.device
+            closed = {
+                "keys": torch.empty(0, dtype=torch.int32, device=dev),
+                "start": torch.empty(0, dtype=torch.int64, device=dev),
+                "end": torch.empty(0, dtype=torch.int64, device=dev),
+                "vals": torch.empty(0, dtype=torch.int64, device=dev),
+            }
+        closed["late"] = _concat_late(lates)
+        return closed
+
     def on_eof(self):
         closed = self.state.close_all()
+        if closed is not None and not self.state.ordered:
+            closed["late"] = None
         return (
             [closed] if closed is not None else [],
             StatefulBatchLogic.RETAIN,
@@ -1249,6 +1292,8 @@ def keyed_session_agg(
     out_cap: int = 1 << 20,
     device: str = "cuda",
     exchange: Optional[bool] = None,
+    ordered: bool = True,
+    max_open: int = 8,
 ) -> Stream[Dict[str, Any]]:
     """Keyed session windows over columnar batches on GPU.
 
@@ -1257,13 +1302,30 @@ def keyed_session_agg(
     (key, ts) on device and one thread walks each key's run in event
     order, so parallelism equals the batch's distinct-key count —
     use the host path's `SessionWindower` for low-cardinality
-    streams.  Ingestion must be watermark-ordered across batches
-    (each batch's events at or after the previous watermark), which
-    in-order sources provide; under that ordering the reference's
-    session merges degenerate to extensions.
+    streams.  With the default ``ordered=True``, ingestion must be
+    watermark-ordered across batches (each batch's events at or after
+    the previous watermark), which in-order sources provide; under
+    that ordering the reference's session merges degenerate to
+    extensions.  Nothing checks the ordering: a disordered batch gives
+    wrong sessions there.
+
+    ``ordered=False`` accepts bounded disorder (multi-partition
+    sources, the multi-rank exchange).  Each key holds up to
+    ``max_open`` (4, 8, 16 or 32) open sessions; a batch is collapsed
+    into gap-separated runs in parallel over its events and the runs
+    are merged into the key's sessions, so an event may extend a
+    session backwards or bridge two sessions into one.  The watermark
+    is the max event ts over all earlier batches (order inside a batch
+    carries no meaning); an event older than ``watermark - wait`` is
+    late: it joins no session and is handed downstream.  Sessions
+    close only once ``last < watermark - wait - gap``, so an accepted
+    event never reaches a closed session.  A key that needs more than
+    ``max_open`` sessions at once raises `RuntimeError`.
 
     Emits dicts of device columns {keys, start, end, vals} at session
-    close / EOF.
+    close / EOF.  With ``ordered=False`` every dict has a fifth entry
+    ``"late"``: a `RecordBatch` of the step's late events or None (a
+    step with late events and no closed session emits empty columns).
     """
     import torch
 
@@ -1286,6 +1348,7 @@ def keyed_session_agg(
         state = SessionAggState(
             torch.device(device), gap_ms, agg_mode,
             slots_pow=slots_pow, out_cap=out_cap,
+            ordered=ordered, max_open=max_open, wait_ms=wait_ms,
         )
         return _DeviceSessionLogic(state, wait_ms, ex, resume_state)
 

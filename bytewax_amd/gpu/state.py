@@ -611,6 +611,18 @@ class SessionAggState:
     ``watermark - gap``.  Role parity: reference
     windowing.py _SessionWindowerLogic under watermark-ordered input
     (in-order ingestion makes merges degenerate to extension).
+
+    ``ordered=False`` drops the ordering assumption: a key's cell
+    holds up to ``max_open`` (4, 8, 16 or 32) open sessions sorted by
+    start, a batch is collapsed into gap-separated runs in parallel
+    over events and merged into the cell, so an event may extend a
+    session backwards or bridge two of them.  The watermark is the
+    max event ts over all earlier batches; an event older than
+    ``watermark - wait_ms`` is late and `insert` hands it back instead
+    of applying it.  Insert never closes a session on this path; only
+    `close_due` (sessions with ``last < watermark - wait_ms - gap``)
+    and `close_all` do.  A key that would need more than ``max_open``
+    sessions raises on the next drain.
     """
 
     def __init__(
@@ -620,14 +632,28 @@ class SessionAggState:
         mode: int = AGG_COUNT,
         slots_pow: int = 20,
         out_cap: int = 1 << 20,
+        ordered: bool = True,
+        max_open: int = 8,
+        wait_ms: int = 0,
     ):
         import torch
 
+        if max_open not in (4, 8, 16, 32):
+            msg = f"max_open must be 4, 8, 16 or 32; got {max_open!r}"
+            raise ValueError(msg)
         self.device = device
         self.cpu = device.type == "cpu"
         self.gap_ms = gap_ms
         self.mode = mode
         self.max_ts_host = 0
+        self.ordered = ordered
+        self.max_open = max_open
+        #: Lateness allowance of the unordered path (ordered mode takes
+        #: it per `close_due` call, as before).
+        self.wait_ms = wait_ms
+        if not ordered:
+            self._init_unordered(slots_pow, out_cap)
+            return
         if self.cpu:
             self._table: Dict[int, Tuple[int, int, int]] = {}
             self._closed: List[Tuple[int, int, int, int]] = []
@@ -749,11 +775,16 @@ class SessionAggState:
         if batch.max_ts is not None and batch.max_ts > self.max_ts_host:
             self.max_ts_host = batch.max_ts
 
-    def insert(self, batch: RecordBatch) -> None:
+    def insert(self, batch: RecordBatch) -> Optional[RecordBatch]:
+        """Apply one batch.  Returns the batch's late events on the
+        unordered path (None if there are none); always None in
+        ordered mode."""
         import torch
 
         if len(batch) == 0:
-            return
+            return None
+        if not self.ordered:
+            return self._insert_unordered(batch)
         if self.cpu:
             self._insert_cpu(batch)
             if (
@@ -791,6 +822,8 @@ class SessionAggState:
             self.max_ts_host = batch.max_ts
 
     def _drain_out(self) -> Optional[Dict[str, Any]]:
+        if not self.ordered:
+            self._check_max_open()
         if self.cpu:
             if not self._closed:
                 return None
@@ -822,9 +855,24 @@ class SessionAggState:
         self.out_n.zero_()
         return out
 
-    def close_due(self, wait_ms: int = 0) -> Optional[Dict[str, Any]]:
+    def close_due(
+        self, wait_ms: Optional[int] = None
+    ) -> Optional[Dict[str, Any]]:
         """Emit sessions idle past watermark - gap (plus any closed by
-        gaps during inserts since the last drain)."""
+        gaps during inserts since the last drain).  The unordered path
+        closes with the allowance it was built with."""
+        if not self.ordered:
+            if wait_ms is not None and wait_ms != self.wait_ms:
+                msg = (
+                    "unordered session state closes with its own "
+                    f"wait_ms={self.wait_ms}; got {wait_ms}"
+                )
+                raise ValueError(msg)
+            return self._close_unordered(
+                self.max_ts_host - self.gap_ms - self.wait_ms
+            )
+        if wait_ms is None:
+            wait_ms = 0
         horizon = self.max_ts_host - self.gap_ms - wait_ms
         if self.cpu:
             for k in list(self._table):
@@ -853,6 +901,8 @@ class SessionAggState:
         self.sacc_alt.zero_()
 
     def close_all(self) -> Optional[Dict[str, Any]]:
+        if not self.ordered:
+            return self._close_unordered(1 << 60)
         if self.cpu:
             for k in list(self._table):
                 s, last, acc = self._table[k]
@@ -871,6 +921,8 @@ class SessionAggState:
     def snapshot_to_host(self) -> Dict[str, Any]:
         import numpy as np
 
+        if not self.ordered:
+            return self._snapshot_unordered()
         if self.cpu:
             items = list(self._table.items())
             return {
@@ -908,6 +960,16 @@ class SessionAggState:
     def restore_from_host(self, snap: Dict[str, Any]) -> None:
         import torch
 
+        if bool(snap.get("ordered", True)) != self.ordered:
+            msg = (
+                "session snapshot was taken with ordered="
+                f"{bool(snap.get('ordered', True))}; this state has "
+                f"ordered={self.ordered}"
+            )
+            raise ValueError(msg)
+        if not self.ordered:
+            self._restore_unordered(snap)
+            return
         self.max_ts_host = snap["max_ts"]
         if self.cpu:
             for k, s, last, acc in zip(
@@ -950,4 +1012,273 @@ class SessionAggState:
             torch.as_tensor(snap["acc"]).to(self.device),
             self.skeys, self.sstart, self.slast, self.sacc,
             self.error_flag,
+        )
+
+    # -- ordered=False: several open sessions per key -------------------
+
+    def _init_unordered(self, slots_pow: int, out_cap: int) -> None:
+        import torch
+
+        self._max_open_hit = False
+        if self.cpu:
+            # key -> [[start, last, acc], ...] sorted by start, any two
+            # neighbours more than the gap apart.
+            self._open: Dict[int, List[List[int]]] = {}
+            self._closed: List[Tuple[int, int, int, int]] = []
+            return
+        device = self.device
+        self.k = ext()
+        self.nslots = 1 << slots_pow
+
+        def table():
+            return (
+                torch.full(
+                    (self.nslots,), -1, dtype=torch.int64, device=device
+                ),
+                torch.zeros(self.nslots, dtype=torch.int32, device=device),
+            ) + tuple(
+                torch.zeros(
+                    (self.nslots, self.max_open),
+                    dtype=torch.int64,
+                    device=device,
+                )
+                for _ in range(3)
+            )
+
+        (
+            self.skeys, self.scnt, self.sstart, self.slast, self.sacc,
+        ) = table()
+        (
+            self.skeys_alt, self.scnt_alt, self.sstart_alt,
+            self.slast_alt, self.sacc_alt,
+        ) = table()
+        self.out_cap = out_cap
+        self.out_keys = torch.empty(out_cap, dtype=torch.int32, device=device)
+        self.out_start = torch.empty(out_cap, dtype=torch.int64, device=device)
+        self.out_end = torch.empty(out_cap, dtype=torch.int64, device=device)
+        self.out_vals = torch.empty(out_cap, dtype=torch.int64, device=device)
+        self.out_n = torch.zeros(1, dtype=torch.int32, device=device)
+        self.max_ts_dev = torch.zeros(1, dtype=torch.int64, device=device)
+        self.error_flag = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def _check_max_open(self) -> None:
+        hit = self._max_open_hit
+        if not self.cpu:
+            hit = (int(self.error_flag.item()) & 2) != 0
+        if hit:
+            msg = (
+                "a key holds more simultaneously open sessions than "
+                f"max_open={self.max_open}; increase max_open"
+            )
+            raise RuntimeError(msg)
+
+    def _split_late(self, batch: RecordBatch):
+        """(accepted, late) by the batch-granular watermark: the max
+        event ts over all EARLIER batches, so a batch's own events
+        never make each other late."""
+        import torch
+
+        cutoff = self.max_ts_host - self.wait_ms
+        if cutoff <= 0:
+            # Timestamps are >= 0: nothing can be late yet.
+            return batch, None
+        late = batch.ts < (cutoff - batch.ts_base)
+        n_late = int(late.sum().item())
+        if n_late == 0:
+            return batch, None
+        n = len(batch)
+
+        def part(keys, ts, vals):
+            return RecordBatch(
+                keys, ts, vals, max_ts=None, ts_base=batch.ts_base
+            )
+
+        if self.cpu:
+            keep = ~late
+            pick = lambda m: part(  # noqa: E731
+                batch.keys[m],
+                batch.ts[m],
+                batch.vals[m] if batch.vals is not None else None,
+            )
+            return (pick(keep) if n_late < n else None), pick(late)
+        ts = batch.ts.to(torch.int64)
+        out = []
+        for mask, kept in ((~late, n - n_late), (late, n_late)):
+            if kept == 0:
+                out.append(None)
+                continue
+            keys_o = torch.empty(kept, dtype=torch.int32, device=self.device)
+            ts_o = torch.empty(kept, dtype=torch.int64, device=self.device)
+            vals_o = torch.empty(
+                kept if batch.vals is not None else 0,
+                dtype=torch.int64,
+                device=self.device,
+            )
+            out_n = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.k.filter_compact(
+                batch.keys, ts, batch.vals, mask.to(torch.uint8),
+                keys_o, ts_o, vals_o, out_n,
+            )
+            out.append(
+                part(keys_o, ts_o, vals_o if batch.vals is not None else None)
+            )
+        return out[0], out[1]
+
+    def _insert_unordered(self, batch: RecordBatch) -> Optional[RecordBatch]:
+        if self.mode == AGG_SUM and batch.vals is None:
+            msg = "sum sessions require a `vals` column"
+            raise ValueError(msg)
+        bmax = batch.max_ts
+        if bmax is None:
+            bmax = int(batch.ts.max().item()) + batch.ts_base
+        accepted, late = self._split_late(batch)
+        if accepted is not None:
+            keys, ts, vals = self._sort(accepted)
+            if self.cpu:
+                self._merge_sorted_cpu(keys, ts, vals)
+            else:
+                runs = self.k.session_run_collapse(
+                    keys.contiguous(), ts.contiguous(),
+                    vals.contiguous() if self.mode == AGG_SUM else None,
+                    self.gap_ms, self.mode,
+                )
+                self.k.session_run_merge(
+                    *runs,
+                    self.skeys, self.scnt, self.sstart, self.slast,
+                    self.sacc, self.max_ts_dev, self.error_flag,
+                    self.gap_ms, self.max_open,
+                )
+        if bmax > self.max_ts_host:
+            self.max_ts_host = bmax
+        return late
+
+    def _merge_sorted_cpu(self, keys, ts, vals) -> None:
+        """Twin of run collapse + run merge: the executable spec."""
+        ks, tl = keys.tolist(), ts.tolist()
+        vl = vals.tolist() if self.mode == AGG_SUM else [1] * len(ks)
+        per_key: Dict[int, List[List[int]]] = {}
+        prev_k = prev_t = None
+        for k, t, v in zip(ks, tl, vl):
+            if k != prev_k or t - prev_t > self.gap_ms:
+                per_key.setdefault(k, []).append([t, t, v])
+            else:
+                run = per_key[k][-1]
+                run[1] = t
+                run[2] += v
+            prev_k, prev_t = k, t
+        for k, runs in per_key.items():
+            self._merge_runs_cpu(k, runs)
+
+    def _merge_runs_cpu(self, k: int, runs: List[List[int]]) -> None:
+        cell = self._open.get(k, [])
+        merged: List[List[int]] = []
+        # Stable sort keeps cell sessions ahead of equal-start runs,
+        # like the kernel's two-pointer merge.
+        for s, last, acc in sorted(cell + runs, key=lambda r: r[0]):
+            if merged and s - merged[-1][1] <= self.gap_ms:
+                cur = merged[-1]
+                cur[1] = max(cur[1], last)
+                cur[2] += acc
+            else:
+                merged.append([s, last, acc])
+        if len(merged) > self.max_open:
+            self._max_open_hit = True  # cell left as it was
+            return
+        self._open[k] = merged
+
+    def _close_unordered(self, horizon: int) -> Optional[Dict[str, Any]]:
+        if self.cpu:
+            for k in list(self._open):
+                cell = self._open[k]
+                p = 0
+                while p < len(cell) and cell[p][1] < horizon:
+                    s, last, acc = cell[p]
+                    self._closed.append((k, s, last, acc))
+                    p += 1
+                if p == len(cell):
+                    del self._open[k]
+                elif p:
+                    self._open[k] = cell[p:]
+            return self._drain_out()
+        self.k.session_multi_close_migrate(
+            self.skeys, self.scnt, self.sstart, self.slast, self.sacc,
+            self.skeys_alt, self.scnt_alt, self.sstart_alt,
+            self.slast_alt, self.sacc_alt,
+            self.out_keys, self.out_start, self.out_end, self.out_vals,
+            self.out_n, self.error_flag, horizon, self.max_open,
+        )
+        for name in ("skeys", "scnt", "sstart", "slast", "sacc"):
+            cur, alt = getattr(self, name), getattr(self, name + "_alt")
+            setattr(self, name, alt)
+            setattr(self, name + "_alt", cur)
+        # The count gates every read of a cell's sessions.
+        self.skeys_alt.fill_(-1)
+        self.scnt_alt.zero_()
+        return self._drain_out()
+
+    def _snapshot_unordered(self) -> Dict[str, Any]:
+        import numpy as np
+        import torch
+
+        if self.cpu:
+            rows = [
+                (k, s, last, acc)
+                for k, cell in self._open.items()
+                for s, last, acc in cell
+            ]
+        else:
+            live = (self.skeys >= 0)[:, None] & (
+                torch.arange(self.max_open, device=self.device)[None, :]
+                < self.scnt[:, None]
+            )
+            keys = self.skeys[:, None].expand(-1, self.max_open)[live]
+            rows = list(
+                zip(
+                    keys.cpu().tolist(),
+                    self.sstart[live].cpu().tolist(),
+                    self.slast[live].cpu().tolist(),
+                    self.sacc[live].cpu().tolist(),
+                )
+            )
+        rows.sort()
+        return {
+            "keys": np.array([r[0] for r in rows], dtype="int32"),
+            "start": np.array([r[1] for r in rows], dtype="int64"),
+            "last": np.array([r[2] for r in rows], dtype="int64"),
+            "acc": np.array([r[3] for r in rows], dtype="int64"),
+            "max_ts": self.max_ts_host,
+            # Insert never closes here, so nothing waits undrained.
+            "pending": [],
+            "ordered": False,
+        }
+
+    def _restore_unordered(self, snap: Dict[str, Any]) -> None:
+        import numpy as np
+        import torch
+
+        self.max_ts_host = snap["max_ts"]
+        n = len(snap["keys"])
+        if n == 0:
+            return
+        # Rows are runs already: sorted by (key, start) they merge
+        # into the table exactly like a collapsed batch.
+        order = np.lexsort((snap["start"], snap["keys"]))
+        cols = [
+            np.asarray(snap[name])[order]
+            for name in ("keys", "start", "last", "acc")
+        ]
+        if self.cpu:
+            per_key: Dict[int, List[List[int]]] = {}
+            for k, s, last, acc in zip(*(c.tolist() for c in cols)):
+                per_key.setdefault(int(k), []).append([s, last, acc])
+            for k, runs in per_key.items():
+                self._merge_runs_cpu(k, runs)
+            return
+        dev = [torch.as_tensor(c).to(self.device) for c in cols]
+        self.k.session_run_merge(
+            dev[0].to(torch.int32), dev[1], dev[2], dev[3],
+            torch.full((1,), n, dtype=torch.int64, device=self.device),
+            self.skeys, self.scnt, self.sstart, self.slast, self.sacc,
+            self.max_ts_dev, self.error_flag,
+            self.gap_ms, self.max_open,
         )

@@ -915,13 +915,22 @@ class _ColumnarSpec:
     wait_ms: int
 
     @staticmethod
-    def resolve(mode, clock, windower) -> Optional["_ColumnarSpec"]:
+    def resolve(mode, clock, windower):
         """Lowerable iff the fold is a device fold, time comes from an
         EventClock (RecordBatch.ts IS the event timestamp), and the
-        windower is tumbling/sliding (sessions keep the dedicated
-        `gpu.operators.keyed_session_agg`)."""
+        windower is tumbling/sliding, or a session windower with a
+        count/sum fold (`_ColumnarSessionSpec`; session min/max/mean
+        stay on the host)."""
         if mode is None or not isinstance(clock, EventClock):
             return None
+        if isinstance(windower, SessionWindower):
+            if mode not in ("count", "sum"):
+                return None
+            return _ColumnarSessionSpec(
+                mode,
+                windower.gap // timedelta(milliseconds=1),
+                clock.wait_for_system_duration // timedelta(milliseconds=1),
+            )
         if isinstance(windower, TumblingWindower):
             len_ms = int(windower.length.total_seconds() * 1000)
             off_ms = len_ms
@@ -1050,6 +1059,106 @@ class _ColumnarWindowLogic(StatefulBatchLogic):
         if final is None:
             return ([], True)
         return ([(COLUMNAR_WINDOW_ID, "E", final)], True)
+
+    def notify_at(self) -> Optional[datetime]:
+        return None
+
+    def snapshot(self):
+        if self.state is None:
+            return {"__columnar__": self._resume}
+        return {"__columnar__": self.state.snapshot_to_host()}
+
+
+@dataclass
+class _ColumnarSessionSpec:
+    """Device-lowering parameters for `SessionWindower` + count/sum."""
+
+    mode: str
+    gap_ms: int
+    wait_ms: int
+
+    def build(self, resume) -> "_ColumnarSessionLogic":
+        return _ColumnarSessionLogic(self, resume)
+
+
+class _ColumnarSessionLogic(StatefulBatchLogic):
+    """The columnar engine behind a lowered session `fold_window`:
+    `SessionAggState(ordered=False)`, so disordered batches merge like
+    the host `_SessionWindowerLogic` and late events are reported.
+
+    Emissions under `COLUMNAR_WINDOW_ID`, one row per closed session
+    (sessions are identified by (key, start)):
+
+    - ``"E"``: `RecordBatch(keys, ts=session start, vals=accumulator)`
+    - ``"M"``: `RecordBatch(keys, ts=session start, vals=session end)`
+    - ``"L"``: the `RecordBatch` of late events
+
+    The watermark is batch-granular: the max event timestamp over all
+    earlier batches, minus the clock's wait.
+    """
+
+    def __init__(self, spec: _ColumnarSessionSpec, resume):
+        self.spec = spec
+        self.state = None  # built on first batch (device known then)
+        self._resume = resume
+
+    def _ensure(self, batch) -> None:
+        if self.state is not None:
+            return
+        from ..gpu import AGG_COUNT, AGG_SUM
+        from ..gpu.state import SessionAggState
+
+        dev = batch.keys.device
+        on_gpu = dev.type != "cpu"
+        self.state = SessionAggState(
+            dev,
+            self.spec.gap_ms,
+            AGG_COUNT if self.spec.mode == "count" else AGG_SUM,
+            slots_pow=20 if on_gpu else 16,
+            out_cap=1 << (20 if on_gpu else 16),
+            ordered=False,
+            wait_ms=self.spec.wait_ms,
+        )
+        if self._resume is not None:
+            self.state.restore_from_host(self._resume)
+            self._resume = None
+
+    @staticmethod
+    def _closed_events(closed) -> List:
+        from ..gpu import RecordBatch
+
+        if closed is None:
+            return []
+        return [
+            (
+                COLUMNAR_WINDOW_ID,
+                "E",
+                RecordBatch(closed["keys"], closed["start"], closed["vals"]),
+            ),
+            (
+                COLUMNAR_WINDOW_ID,
+                "M",
+                RecordBatch(closed["keys"], closed["start"], closed["end"]),
+            ),
+        ]
+
+    def on_batch(self, values) -> Tuple[Iterable, bool]:
+        events: List = []
+        for batch in values:
+            self._ensure(batch)
+            late = self.state.insert(batch)
+            if late is not None:
+                events.append((COLUMNAR_WINDOW_ID, "L", late))
+        events.extend(self._closed_events(self.state.close_due()))
+        return (events, False)
+
+    def on_notify(self) -> Tuple[Iterable, bool]:
+        return ([], False)
+
+    def on_eof(self) -> Tuple[Iterable, bool]:
+        if self.state is None:
+            return ([], True)
+        return (self._closed_events(self.state.close_all()), True)
 
     def notify_at(self) -> Optional[datetime]:
         return None
