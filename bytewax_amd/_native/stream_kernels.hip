@@ -1142,13 +1142,28 @@ __global__ void k_overflow_agg(
   }
 }
 
+// 16-byte view of two adjacent packed entries (one vector load).
+typedef unsigned long long agg_u64x2 __attribute__((ext_vector_type(2)));
+
+// Segment aggregation: one workgroup folds one scatter segment into an
+// LDS open-address table, then flushes each distinct key once.
+//
+// The segment is streamed with a register double buffer: every thread
+// keeps R independent 16-byte loads (two packed entries each) of chunk
+// i+1 in flight while it probes chunk i, so a 1024-thread block has
+// R * 16 KiB of HBM reads outstanding instead of one 8-byte load per
+// lane (the probe loop's data-dependent exits keep the compiler from
+// hoisting loads on its own).  A segment that starts only 8-byte
+// aligned (fixed layout, odd `cap`) peels one head entry, and an odd
+// remainder one tail entry, so no vector load is ever misaligned or
+// reaches past `min(count, cap)`.
 template <int MODE>
 __global__ __launch_bounds__(1024) void k_radix_agg(
     const uint64_t* __restrict__ ev_packed,
     const int64_t* __restrict__ ev_vals,
-    const int* __restrict__ offsets,
     const int* __restrict__ counts,
-    int64_t clamp_cap,  // 0 = counts are exact; >0 = clamp (fixed layout)
+    int64_t cap,  // segment stride: segment b owns [b*cap, (b+1)*cap);
+                  // counts past it went to the overflow spill
     uint64_t* __restrict__ tkeys,
     unsigned long long* __restrict__ tvals,
     uint64_t mask,
@@ -1168,13 +1183,13 @@ __global__ __launch_bounds__(1024) void k_radix_agg(
   __syncthreads();
   int b = blockIdx.x;
   int cnt = counts[b];
-  if (clamp_cap > 0 && cnt > (int)clamp_cap) cnt = (int)clamp_cap;
-  int start = offsets[b];
-  for (int j = threadIdx.x; j < cnt; j += blockDim.x) {
-    uint64_t packed = ev_packed[start + j];
-    if (packed == EMPTY_SLOT) continue;  // staged-scatter pad
-    unsigned long long inc =
-        (MODE == AGG_SUM) ? (unsigned long long)ev_vals[start + j] : 1ULL;
+  if (cnt > (int)cap) cnt = (int)cap;
+  const uint64_t* seg = ev_packed + (int64_t)b * cap;
+  const int64_t* segv =
+      (MODE == AGG_SUM) ? ev_vals + (int64_t)b * cap : nullptr;
+
+  auto add = [&](uint64_t packed, unsigned long long inc) {
+    if (packed == EMPTY_SLOT) return;  // staged-scatter pad
     uint64_t h64 = mix64(packed);
     int lh = (int)((h64 >> 32) & (region - 1));
     bool done = false;
@@ -1201,6 +1216,63 @@ __global__ __launch_bounds__(1024) void k_radix_agg(
       // at least as full): flush straight to the global region.
       if (!hash_add(tkeys, tvals, mask, region_bits, packed, inc)) {
         atomicExch(error_flag, 1);
+      }
+    }
+  };
+
+  // Head/tail entries outside the 16-byte-aligned vector body.
+  const int head = (cnt > 0 && ((uintptr_t)seg & 15) != 0) ? 1 : 0;
+  const int nvec = (cnt - head) >> 1;
+  const int tail = head + 2 * nvec;  // == cnt or cnt - 1
+  if (threadIdx.x == 0 && head) {
+    add(seg[0], MODE == AGG_SUM ? (unsigned long long)segv[0] : 1ULL);
+  }
+  if (threadIdx.x == blockDim.x - 1 && tail < cnt) {
+    add(seg[tail],
+        MODE == AGG_SUM ? (unsigned long long)segv[tail] : 1ULL);
+  }
+
+  // SUM carries the two values next to each pair, so it keeps half the
+  // depth to stay inside the 128-VGPR budget of a 1024-thread block.
+  constexpr int R = (MODE == AGG_SUM) ? 2 : 4;
+  const agg_u64x2* vseg = (const agg_u64x2*)(seg + head);
+  const int64_t* vval = (MODE == AGG_SUM) ? segv + head : nullptr;
+  const int T = (int)blockDim.x;
+  const int chunk = R * T;
+  agg_u64x2 cur_p[R], nxt_p[R];
+  unsigned long long cur_v[R][2], nxt_v[R][2];
+  auto fetch = [&](agg_u64x2 (&bp)[R], unsigned long long (&bv)[R][2],
+                   int base) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int v = base + r * T + (int)threadIdx.x;
+      if (v < nvec) {
+        bp[r] = vseg[v];
+        if (MODE == AGG_SUM) {
+          bv[r][0] = (unsigned long long)vval[2 * v];
+          bv[r][1] = (unsigned long long)vval[2 * v + 1];
+        }
+      } else {
+        bp[r] = agg_u64x2{EMPTY_SLOT, EMPTY_SLOT};
+        if (MODE == AGG_SUM) bv[r][0] = bv[r][1] = 0;
+      }
+    }
+  };
+  if (nvec > 0) fetch(cur_p, cur_v, 0);
+  for (int base = 0; base < nvec; base += chunk) {
+    // Issue the next chunk's loads before touching the LDS table.
+    if (base + chunk < nvec) fetch(nxt_p, nxt_v, base + chunk);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      add(cur_p[r].x, MODE == AGG_SUM ? cur_v[r][0] : 1ULL);
+      add(cur_p[r].y, MODE == AGG_SUM ? cur_v[r][1] : 1ULL);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      cur_p[r] = nxt_p[r];
+      if (MODE == AGG_SUM) {
+        cur_v[r][0] = nxt_v[r][0];
+        cur_v[r][1] = nxt_v[r][1];
       }
     }
   }
@@ -2909,7 +2981,9 @@ void radix_window_insert(
     if (env_blocks > 0 && (unsigned)env_blocks < gx) gx = (unsigned)env_blocks;
     if (kind == SCAT_STAGED) {
       // One tile = blockDim * U events; enough blocks to fill the
-      // chip at the LDS-bounded occupancy, few enough to keep the
+      // chip at the REGISTER-bounded occupancy (98 VGPRs: two
+      // 512-thread workgroups per CU, where the 40 KB staging LDS
+      // alone would allow four), few enough to keep the
       // end-of-kernel residual padding small.  U (events per thread
       // per tile) tunable via BYTEWAX_SCATTER_U (8/16/32).
       int su = 16;
@@ -2979,10 +3053,7 @@ void radix_window_insert(
     else scat_any(ts.data_ptr<int64_t>(), sg);
   }
 
-  // Fixed layout: segment b's events live at [b*cap, b*cap + count).
-  auto offsets = at::arange(
-      nseg, at::TensorOptions().dtype(at::kInt).device(keys.device()));
-  offsets = offsets * (int)cap;
+  // Segment b's events live at [b*cap, b*cap + count).
   size_t agg_lds = (size_t)16 << seg_bits;
   dim3 agg_block(seg_bits >= 12 ? 1024 : 256);
   auto agg = [&](auto kern) {
@@ -2990,7 +3061,7 @@ void radix_window_insert(
         kern, dim3((unsigned)nseg), agg_block, agg_lds, stream,
         (const uint64_t*)ev_packed.data_ptr<int64_t>(),
         mode == AGG_SUM ? ev_vals.data_ptr<int64_t>() : nullptr,
-        offsets.data_ptr<int32_t>(), gcursors.data_ptr<int32_t>(), cap,
+        gcursors.data_ptr<int32_t>(), cap,
         (uint64_t*)tkeys.data_ptr<int64_t>(),
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
         (int)region_bits, seg_bits, error_flag.data_ptr<int32_t>());
@@ -3240,9 +3311,6 @@ void radix_agg_only(
       cap = ev_packed.numel() / nseg;
     }
   }
-  auto offsets = at::arange(
-      nseg, at::TensorOptions().dtype(at::kInt).device(tkeys.device()));
-  offsets = offsets * (int)cap;
   size_t agg_lds = (size_t)16 << seg_bits;
   dim3 agg_block(seg_bits >= 12 ? 1024 : 256);
   auto agg = [&](auto kern) {
@@ -3250,7 +3318,7 @@ void radix_agg_only(
         kern, dim3((unsigned)nseg), agg_block, agg_lds, stream,
         (const uint64_t*)ev_packed.data_ptr<int64_t>(),
         mode == AGG_SUM ? ev_vals.data_ptr<int64_t>() : nullptr,
-        offsets.data_ptr<int32_t>(), gcursors.data_ptr<int32_t>(), cap,
+        gcursors.data_ptr<int32_t>(), cap,
         (uint64_t*)tkeys.data_ptr<int64_t>(),
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
         (int)region_bits, seg_bits, error_flag.data_ptr<int32_t>());
@@ -4604,7 +4672,6 @@ int64_t native_run_window_steps(
   hipStream_t sc_stream = nullptr;
   hipEvent_t ev_sc[2] = {nullptr, nullptr};
   hipEvent_t ev_ag[2] = {nullptr, nullptr};
-  torch::Tensor agg_offsets;
   int64_t nb = 0, cap = 0, nseg = 0;
   int seg_bits = (int)region_bits;
   ScatterKind kind = SCAT_FIXED;
@@ -4651,10 +4718,6 @@ int64_t native_run_window_steps(
         cap = ev_packed->numel() / nseg;
       }
     }
-    agg_offsets = at::arange(
-        nseg,
-        at::TensorOptions().dtype(at::kInt).device(tkeys.device()));
-    agg_offsets = agg_offsets * (int)cap;
     HIP_CHECK(hipStreamCreateWithFlags(&sc_stream, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
       HIP_CHECK(hipEventCreateWithFlags(&ev_sc[i], hipEventDisableTiming));
@@ -4764,8 +4827,7 @@ int64_t native_run_window_steps(
         hipLaunchKernelGGL(
             k_radix_agg<AGG_COUNT>, dim3((unsigned)nseg), agg_block,
             agg_lds, stream, (const uint64_t*)evp.data_ptr<int64_t>(),
-            (const int64_t*)nullptr, agg_offsets.data_ptr<int32_t>(),
-            gcur.data_ptr<int32_t>(), cap,
+            (const int64_t*)nullptr, gcur.data_ptr<int32_t>(), cap,
             (uint64_t*)cur_k.data_ptr<int64_t>(),
             (unsigned long long*)cur_v.data_ptr<int64_t>(), mask,
             (int)region_bits, seg_bits, error_flag.data_ptr<int32_t>());
