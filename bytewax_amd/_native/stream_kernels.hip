@@ -176,7 +176,75 @@ __device__ __forceinline__ uint64_t find_slot_r(
     uint64_t* __restrict__ tkeys, uint64_t mask, int region_bits,
     uint64_t packed);
 
-template <int MODE, bool DEDUP, typename TS = int64_t>
+// Late-event side output of the tumbling/sliding insert kernels (the
+// `LATE` instantiations).  An event with absolute `t < late_cutoff`
+// joins no window: its (key, t, val) row is appended to the late
+// buffer instead and the event is dropped from everything downstream
+// of the timestamp read (histograms, table, watermark).  The cursor
+// `late_n` is never reset here: rows accumulate across inserts until
+// the host drains them.
+//
+// Append is wave-aggregated like k_close_extract: ballot, one
+// atomicAdd per wave by the first late lane, popcount rank.  Safe
+// under divergence (tile tails, grid-stride tails): only active lanes
+// vote and the leader is by construction an active lane.  The two
+// radix scatters aggregate once more per workgroup: the waves reserve
+// on an LDS counter and one thread moves the block's total to
+// `late_n`, so even a stream with a sparse sprinkle of late events
+// (most waves holding one) sends one global atomic per tile / block
+// to that single address instead of one per wave.  A row that would
+// land at or past `late_cap` sets ERR_LATE_OVERFLOW; the host keeps an
+// upper bound on undrained rows so this is a guard only.  `error_flag`
+// is a bit set: bit 0 (table / spill overflow) is OR-ed in everywhere,
+// never stored over the word, so the two causes stay distinct.
+#define ERR_LATE_OVERFLOW 2
+#define NO_LATE_ARGS                                                \
+  (int64_t)0, (int32_t*)nullptr, (int64_t*)nullptr,                 \
+      (int64_t*)nullptr, (int*)nullptr, (int64_t)0
+
+// Wave-aggregated reservation on `counter` (global or LDS): the
+// position of this lane among the takers; meaningful only where
+// `take`.
+__device__ __forceinline__ int wave_reserve(bool take, int* counter) {
+  unsigned long long ball = __ballot(take);
+  if (ball == 0) return 0;
+  int lane = threadIdx.x & (WAVE - 1);
+  int lead = __ffsll(ball) - 1;
+  int base = 0;
+  if (lane == lead) base = atomicAdd(counter, __popcll(ball));
+  base = __shfl(base, lead);
+  return base + __popcll(ball & ((1ULL << lane) - 1ULL));
+}
+
+template <bool HAS_VAL>
+__device__ __forceinline__ void late_store(
+    int64_t idx, int32_t key, int64_t t, int64_t v,
+    int32_t* __restrict__ late_keys, int64_t* __restrict__ late_ts,
+    int64_t* __restrict__ late_vals, int64_t late_cap,
+    int* __restrict__ error_flag) {
+  if (idx >= 0 && idx < late_cap) {
+    late_keys[idx] = key;
+    late_ts[idx] = t;
+    if (HAS_VAL) late_vals[idx] = v;
+  } else {
+    atomicOr(error_flag, ERR_LATE_OVERFLOW);
+  }
+}
+
+template <bool HAS_VAL>
+__device__ __forceinline__ void late_append(
+    bool is_late, int32_t key, int64_t t, int64_t v,
+    int32_t* __restrict__ late_keys, int64_t* __restrict__ late_ts,
+    int64_t* __restrict__ late_vals, int* __restrict__ late_n,
+    int64_t late_cap, int* __restrict__ error_flag) {
+  int pos = wave_reserve(is_late, late_n);
+  if (is_late) {
+    late_store<HAS_VAL>(pos, key, t, v, late_keys, late_ts, late_vals,
+                        late_cap, error_flag);
+  }
+}
+
+template <int MODE, bool DEDUP, typename TS = int64_t, bool LATE = false>
 __global__ void k_window_agg_insert(
     const int32_t* __restrict__ keys,
     const TS* __restrict__ ts,
@@ -195,9 +263,16 @@ __global__ void k_window_agg_insert(
     int region_bits,  // table layout (see hash_add)
     unsigned long long* __restrict__ max_ts,  // device scalar (atomicMax)
     int* __restrict__ error_flag,
-    const int64_t* __restrict__ ts_base_dev) {  // extra device-side
+    const int64_t* __restrict__ ts_base_dev,  // extra device-side
                       // offset, lets a captured hipGraph be replayed
                       // with advancing timestamps (see k_bump)
+    int64_t late_cutoff,  // LATE only (see late_append)
+    int32_t* __restrict__ late_keys,
+    int64_t* __restrict__ late_ts,
+    int64_t* __restrict__ late_vals,  // unused for COUNT
+    int* __restrict__ late_n,
+    int64_t late_cap) {
+  static_assert(!(LATE && DEDUP), "late tracking excludes the dedup path");
   if (ts_base_dev != nullptr) ts_base += *ts_base_dev;
   int lane = threadIdx.x & (WAVE - 1);
   int64_t stride = gridDim.x * (int64_t)blockDim.x;
@@ -209,6 +284,20 @@ __global__ void k_window_agg_insert(
   for (int64_t i = first; i - lane < n; i += stride) {
     bool valid = i < n;
     int64_t t = valid ? ((int64_t)ts[i] + ts_base) : 0;
+    if constexpr (LATE) {
+      // Before the sliding expansion: a late event joins none of its
+      // windows, open or not.
+      bool is_late = valid && t < late_cutoff;
+      int64_t lv = 0;
+      if (MODE == AGG_SUM && is_late) lv = vals[i];
+      late_append<MODE == AGG_SUM>(
+          is_late, is_late ? keys[i] : 0, t, lv, late_keys, late_ts,
+          late_vals, late_n, late_cap, error_flag);
+      if (is_late) {
+        valid = false;
+        t = 0;
+      }
+    }
     if (t > local_max) local_max = t;
     uint64_t packed = 0;
     unsigned long long inc = 0;
@@ -230,7 +319,7 @@ __global__ void k_window_agg_insert(
           uint64_t p2 =
               ((uint64_t)(uint32_t)(int32_t)wn << 32) | (uint32_t)keys[i];
           if (!hash_add(tkeys, tvals, mask, region_bits, p2, inc)) {
-            atomicExch(error_flag, 1);
+            atomicOr(error_flag, 1);
           }
         }
       }
@@ -274,7 +363,7 @@ __global__ void k_window_agg_insert(
     } else if (valid) {
       ok = hash_add(tkeys, tvals, mask, region_bits, packed, inc);
     }
-    if (!ok) atomicExch(error_flag, 1);
+    if (!ok) atomicOr(error_flag, 1);
   }
   // Wave-reduce the max timestamp, one atomic per wave.
   for (int off = WAVE / 2; off > 0; off >>= 1) {
@@ -365,7 +454,7 @@ __global__ __launch_bounds__(512) void k_scatter_coarse(
           if (rp < res_cap) {
             ev_res[(int64_t)cb * res_cap + rp] = packed;
           } else {
-            atomicExch(error_flag, 1);
+            atomicOr(error_flag, 1);
           }
         }
       }
@@ -388,7 +477,7 @@ __global__ __launch_bounds__(512) void k_scatter_coarse(
             if (rp < res_cap) {
               ev_res[(int64_t)b * res_cap + rp] = stage[b][g * 8 + q];
             } else {
-              atomicExch(error_flag, 1);
+              atomicOr(error_flag, 1);
             }
           }
         }
@@ -410,7 +499,7 @@ __global__ __launch_bounds__(512) void k_scatter_coarse(
       if (rp < res_cap) {
         ev_res[(int64_t)b * res_cap + rp] = stage[b][q];
       } else {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       }
     }
   }
@@ -469,7 +558,7 @@ __global__ __launch_bounds__(256) void k_agg_cached(
       lh = (lh + 1) & (V2_CACHE - 1);
     }
     if (!hash_add(tkeys, tvals, mask, region_bits, packed, 1ULL)) {
-      atomicExch(error_flag, 1);
+      atomicOr(error_flag, 1);
     }
   };
 
@@ -489,7 +578,7 @@ __global__ __launch_bounds__(256) void k_agg_cached(
   for (int s = threadIdx.x; s < V2_CACHE; s += blockDim.x) {
     if (ckeys[s] != EMPTY_SLOT) {
       if (!hash_add(tkeys, tvals, mask, region_bits, ckeys[s], cvals[s])) {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       }
     }
   }
@@ -552,7 +641,7 @@ static inline void magic_div_u64(
 // TS is int64_t (absolute ms) or int32_t (deltas from `ts_base`, the
 // wire format of the RCCL exchange — inserting the received segments
 // directly skips the int64 timestamp rebuild entirely).
-template <int MODE, typename TS = int64_t>
+template <int MODE, typename TS = int64_t, bool LATE = false>
 __global__ void k_radix_scatter_fixed(
     const int32_t* __restrict__ keys,
     const TS* __restrict__ ts,
@@ -575,18 +664,37 @@ __global__ void k_radix_scatter_fixed(
     unsigned long long* __restrict__ max_ts,
     int* __restrict__ error_flag,
     uint64_t win_m2,
-    uint64_t win_maxfast) {
+    uint64_t win_maxfast,
+    int64_t late_cutoff,  // LATE only (see late_append)
+    int32_t* __restrict__ late_keys,
+    int64_t* __restrict__ late_ts,
+    int64_t* __restrict__ late_vals,  // unused for COUNT
+    int* __restrict__ late_n,
+    int64_t late_cap) {
+  static_assert(!(LATE && MODE == AGG_TS), "no late tracking for AGG_TS");
   extern __shared__ int lmem[];
+  // LATE: [0] the block's late rows (pass 1), then their placement
+  // cursor (pass 2); [1] the block's base in the late buffer.
+  __shared__ int s_late[LATE ? 2 : 1];
   int nb = (int)(((mask + 1) >> region_bits));
   int* lhist = lmem;
   int* lbase = lmem + nb;
   for (int b = threadIdx.x; b < nb; b += blockDim.x) lhist[b] = 0;
+  if constexpr (LATE) {
+    if (threadIdx.x == 0) s_late[0] = 0;
+  }
   __syncthreads();
   int64_t start = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t stride = gridDim.x * (int64_t)blockDim.x;
   int64_t local_max = 0;
   for (int64_t i = start; i < n; i += stride) {
     int64_t t = (int64_t)ts[i] + ts_base;
+    if constexpr (LATE) {
+      // Counted here, stored by the placement pass; skipped by both.
+      bool is_late = t < late_cutoff;
+      wave_reserve(is_late, &s_late[0]);
+      if (is_late) continue;
+    }
     if (t > local_max) local_max = t;
     uint64_t packed;
     int nwin = 1;
@@ -614,9 +722,26 @@ __global__ void k_radix_scatter_fixed(
     lbase[b] = lhist[b] > 0 ? atomicAdd(&gcursors[b], lhist[b]) : 0;
     lhist[b] = 0;
   }
+  if constexpr (LATE) {
+    if (threadIdx.x == 0) {
+      s_late[1] = s_late[0] > 0 ? atomicAdd(late_n, s_late[0]) : 0;
+      s_late[0] = 0;
+    }
+  }
   __syncthreads();
   for (int64_t i = start; i < n; i += stride) {
     int64_t t = (int64_t)ts[i] + ts_base;
+    if constexpr (LATE) {
+      bool is_late = t < late_cutoff;
+      int lpos = wave_reserve(is_late, &s_late[0]);
+      if (is_late) {
+        late_store<MODE == AGG_SUM>(
+            (int64_t)s_late[1] + lpos, keys[i], t,
+            MODE == AGG_SUM ? vals[i] : 0, late_keys, late_ts, late_vals,
+            late_cap, error_flag);
+        continue;
+      }
+    }
     uint64_t packed;
     int nwin = 1;
     if (MODE == AGG_TS) {
@@ -642,7 +767,7 @@ __global__ void k_radix_scatter_fixed(
           ov_packed[opos] = packed;
           if (MODE != AGG_COUNT) ov_vals[opos] = v;
         } else {
-          atomicExch(error_flag, 1);
+          atomicOr(error_flag, 1);
         }
       }
       packed -= (uint64_t)1 << 32;
@@ -711,7 +836,7 @@ __global__ void k_radix_scatter_direct(
         ov_packed[opos] = packed;
         if (MODE == AGG_SUM) ov_vals[opos] = v;
       } else {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       }
     }
   }
@@ -743,7 +868,8 @@ __global__ void k_radix_scatter_direct(
 // 2^(seg_bits-region_bits) regions per block.
 #define SC_GRAN 8  // events per cursor reservation = one 64 B line
 
-template <int MODE, typename TS = int64_t, int U = 16, int BLK = 256>
+template <int MODE, typename TS = int64_t, int U = 16, int BLK = 256,
+          bool LATE = false>
 __global__ __launch_bounds__(BLK) void k_radix_scatter_staged(
     const int32_t* __restrict__ keys,
     const TS* __restrict__ ts,
@@ -766,8 +892,18 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged(
     unsigned long long* __restrict__ max_ts,
     int* __restrict__ error_flag,
     uint64_t win_m2,
-    uint64_t win_maxfast) {
+    uint64_t win_maxfast,
+    int64_t late_cutoff,  // LATE only (see late_append)
+    int32_t* __restrict__ late_keys,
+    int64_t* __restrict__ late_ts,
+    int64_t* __restrict__ late_vals,  // unused for COUNT
+    int* __restrict__ late_n,
+    int64_t late_cap) {
+  static_assert(!(LATE && MODE == AGG_TS), "no late tracking for AGG_TS");
   extern __shared__ char smem[];
+  // LATE: [0] late rows of the current tile, [1] their base in the
+  // late buffer (reserved in P2, consumed in P3b).
+  __shared__ int s_late[LATE ? 2 : 1];
   const int nseg = (int)(((mask + 1) >> seg_bits));
   uint64_t* res = (uint64_t*)smem;  // [nseg][SC_GRAN] residual staging
   int64_t* res_v =
@@ -781,6 +917,9 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged(
   for (int b = threadIdx.x; b < nseg; b += blockDim.x) {
     res_cnt[b] = 0;
     lhist[b] = 0;
+  }
+  if constexpr (LATE) {
+    if (threadIdx.x == 0) s_late[0] = 0;
   }
   __syncthreads();
 
@@ -796,7 +935,7 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged(
         ov_packed[opos] = packed;
         if (MODE != AGG_COUNT) ov_vals[opos] = v;
       } else {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       }
     }
   };
@@ -813,6 +952,21 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged(
     for (int u = 0; u < U; ++u) {
       int64_t i = t0 + (int64_t)u * blockDim.x + threadIdx.x;
       sg[u] = -1;
+      if constexpr (LATE) {
+        // Every lane of the wave votes (tail lanes as "not late").  A
+        // late event never reaches the tile histogram; it keeps a
+        // negative sg[u] (-2, which P3b turns into the late row) and
+        // its rank within the tile in nw[u].
+        bool in = i < n;
+        int64_t tl = in ? ((int64_t)ts[i] + ts_base) : 0;
+        bool is_late = in && tl < late_cutoff;
+        int lpos = wave_reserve(is_late, &s_late[0]);
+        if (is_late) {
+          sg[u] = -2;
+          nw[u] = lpos;
+          continue;
+        }
+      }
       if (i >= n) continue;
       int64_t t = (int64_t)ts[i] + ts_base;
       if (t > local_max) local_max = t;
@@ -856,6 +1010,10 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged(
       lofs[b] = res_cnt[b];
       lhist[b] = grant;
     }
+    if constexpr (LATE) {
+      if (threadIdx.x == 0)
+        s_late[1] = s_late[0] > 0 ? atomicAdd(late_n, s_late[0]) : 0;
+    }
     __syncthreads();
     // P3a: drain old residual into the granted granule (granule >=
     // SC_GRAN > residual when granted, so all-or-nothing).
@@ -875,6 +1033,15 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged(
     // P3b: place this tile's (possibly window-expanded) entries at
     // their virtual positions.
     for (int u = 0; u < U; ++u) {
+      if constexpr (LATE) {
+        if (sg[u] == -2) {
+          int64_t i = t0 + (int64_t)u * blockDim.x + threadIdx.x;
+          late_store<MODE == AGG_SUM>(
+              (int64_t)s_late[1] + nw[u], keys[i], (int64_t)ts[i] + ts_base,
+              MODE == AGG_SUM ? vals[i] : 0, late_keys, late_ts, late_vals,
+              late_cap, error_flag);
+        }
+      }
       if (sg[u] < 0) continue;
       uint64_t p2 = pk[u];
       for (int w = 0; w < nw[u]; ++w) {
@@ -898,6 +1065,9 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged(
     for (int b = threadIdx.x; b < nseg; b += blockDim.x) {
       res_cnt[b] = lofs[b] - lhist[b];
       lhist[b] = 0;
+    }
+    if constexpr (LATE) {
+      if (threadIdx.x == 0) s_late[0] = 0;
     }
     __syncthreads();
   }
@@ -981,7 +1151,7 @@ __global__ __launch_bounds__(256) void k_radix_scatter_staged2(
   auto spill = [&](uint64_t packed) {
     int opos = atomicAdd(ov_cursor, 1);
     if (opos < ov_cap) ov_packed[opos] = packed;
-    else atomicExch(error_flag, 1);
+    else atomicOr(error_flag, 1);
   };
 
   const int64_t tile = (int64_t)blockDim.x * U;
@@ -1137,7 +1307,7 @@ __global__ void k_overflow_agg(
     unsigned long long inc =
         (MODE == AGG_SUM) ? (unsigned long long)ov_vals[i] : 1ULL;
     if (!hash_add(tkeys, tvals, mask, region_bits, ov_packed[i], inc)) {
-      atomicExch(error_flag, 1);
+      atomicOr(error_flag, 1);
     }
   }
 }
@@ -1215,7 +1385,7 @@ __global__ __launch_bounds__(1024) void k_radix_agg(
       // LDS staging full (only possible when the global regions are
       // at least as full): flush straight to the global region.
       if (!hash_add(tkeys, tvals, mask, region_bits, packed, inc)) {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       }
     }
   };
@@ -1282,7 +1452,7 @@ __global__ __launch_bounds__(1024) void k_radix_agg(
   for (int s = threadIdx.x; s < region; s += blockDim.x) {
     if (lkeys[s] != EMPTY_SLOT) {
       if (!hash_add(tkeys, tvals, mask, region_bits, lkeys[s], lvals[s])) {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       }
     }
   }
@@ -1308,7 +1478,7 @@ __global__ void k_overflow_agg_stats(
   for (; i < n; i += stride) {
     uint64_t slot = find_slot(tkeys, mask, ov_packed[i]);
     if (slot == ~0ULL) {
-      atomicExch(error_flag, 1);
+      atomicOr(error_flag, 1);
       continue;
     }
     long long v = ov_vals[i];
@@ -1390,7 +1560,7 @@ __global__ __launch_bounds__(1024) void k_radix_agg_stats(
       // LDS region full: fall through to the global region directly.
       uint64_t gslot = find_slot(tkeys, mask, packed);
       if (gslot == ~0ULL) {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       } else {
         atomicAdd((unsigned long long*)&tcnt[gslot], 1ULL);
         atomicAdd((unsigned long long*)&tsum[gslot], (unsigned long long)v);
@@ -1404,7 +1574,7 @@ __global__ __launch_bounds__(1024) void k_radix_agg_stats(
     if (lkeys[s] != EMPTY_SLOT) {
       uint64_t gslot = find_slot(tkeys, mask, lkeys[s]);
       if (gslot == ~0ULL) {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
         continue;
       }
       atomicAdd((unsigned long long*)&tcnt[gslot],
@@ -1498,7 +1668,7 @@ __global__ void k_close_migrate(
       take = (int64_t)win < win_hi;
       if (!take) {
         if (!hash_add(nkeys, nvals, mask, region_bits, k, tvals[i])) {
-          atomicExch(error_flag, 1);
+          atomicOr(error_flag, 1);
         }
       }
     }
@@ -1561,6 +1731,7 @@ __device__ __forceinline__ uint64_t find_slot(
 
 // 1BRC-style keyed running stats: count / sum / min / max per
 // (key, window).  One pass over the batch, four atomics per event.
+template <bool LATE = false>
 __global__ void k_stats_insert(
     const int32_t* __restrict__ keys,
     const int64_t* __restrict__ ts,
@@ -1576,19 +1747,32 @@ __global__ void k_stats_insert(
     int64_t len_ms,
     int64_t ts_base,
     unsigned long long* __restrict__ max_ts,
-    int* __restrict__ error_flag) {
+    int* __restrict__ error_flag,
+    int64_t late_cutoff,  // LATE only (see late_append)
+    int32_t* __restrict__ late_keys,
+    int64_t* __restrict__ late_ts,
+    int64_t* __restrict__ late_vals,
+    int* __restrict__ late_n,
+    int64_t late_cap) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t stride = gridDim.x * (int64_t)blockDim.x;
   int64_t local_max = 0;
   for (; i < n; i += stride) {
     int64_t t = ts[i] + ts_base;
+    if constexpr (LATE) {
+      bool is_late = t < late_cutoff;
+      late_append<true>(
+          is_late, is_late ? keys[i] : 0, t, is_late ? vals[i] : 0,
+          late_keys, late_ts, late_vals, late_n, late_cap, error_flag);
+      if (is_late) continue;
+    }
     if (t > local_max) local_max = t;
     int64_t win = (t - align_ms) / len_ms;
     uint64_t packed =
         ((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)keys[i];
     uint64_t slot = find_slot(tkeys, mask, packed);
     if (slot == ~0ULL) {
-      atomicExch(error_flag, 1);
+      atomicOr(error_flag, 1);
       continue;
     }
     long long v = vals[i];
@@ -1715,7 +1899,7 @@ __device__ __forceinline__ void join_apply(
                       // deduped caller must restore it
   uint64_t slot = find_slot_r(tkeys, mask, region_bits, packed);
   if (slot == ~0ULL) {
-    atomicExch(error_flag, 1);
+    atomicOr(error_flag, 1);
     return;
   }
   if (side == 0) {
@@ -2029,7 +2213,7 @@ __global__ void k_session_insert(
     uint64_t key = (uint64_t)(uint32_t)keys[i];
     uint64_t slot = session_find_or_claim(skeys, mask, key);
     if (slot == ~0ULL) {
-      atomicExch(error_flag, 1);
+      atomicOr(error_flag, 1);
       continue;
     }
     // This thread owns the key's whole segment; no other thread
@@ -2049,7 +2233,7 @@ __global__ void k_session_insert(
           out_end[idx] = last;
           out_vals[idx] = acc;
         } else {
-          atomicExch(error_flag, 1);
+          atomicOr(error_flag, 1);
         }
         open = false;
       }
@@ -2117,12 +2301,12 @@ __global__ void k_session_close_migrate(
         out_end[idx] = last;
         out_vals[idx] = sacc[i];
       } else {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       }
     } else {
       uint64_t slot = session_find_or_claim(dst_keys, mask, key);
       if (slot == ~0ULL) {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
         continue;
       }
       dst_start[slot] = sstart[i];
@@ -2592,7 +2776,7 @@ __global__ void k_dict_insert(
         if (prev == lo) break;
       }
       h = (h + 1) & mask;
-      if (probes == mask) atomicExch(error_flag, 1);  // table full
+      if (probes == mask) atomicOr(error_flag, 1);  // table full
     }
   }
 }
@@ -2657,7 +2841,7 @@ __global__ void k_dict_insert_pinned(
         break;
       }
       h = (h + 1) & mask;
-      if (probes == mask) atomicExch(error_flag, 1);
+      if (probes == mask) atomicOr(error_flag, 1);
     }
   }
 }
@@ -2750,7 +2934,46 @@ static void check_dev(const torch::Tensor& t, torch::ScalarType st,
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
-void window_agg_insert(
+// Host view of the late-event side output (see late_append).  The
+// insert launchers take a pointer: nullptr selects the default
+// instantiations, exactly the launches the plain entry points always
+// made.
+struct LateSink {
+  int64_t cutoff;
+  int32_t* keys;
+  int64_t* ts;
+  int64_t* vals;  // nullptr for COUNT
+  int* n;
+  int64_t cap;
+};
+
+static LateSink make_late_sink(
+    int64_t late_cutoff,
+    torch::Tensor& late_keys,
+    torch::Tensor& late_ts,
+    c10::optional<torch::Tensor>& late_vals,
+    torch::Tensor& late_n,
+    bool need_vals) {
+  check_dev(late_keys, torch::kInt32, "late_keys");
+  check_dev(late_ts, torch::kInt64, "late_ts");
+  check_dev(late_n, torch::kInt32, "late_n");
+  int64_t cap = late_keys.numel();
+  TORCH_CHECK(late_ts.numel() >= cap, "late_ts smaller than late_keys");
+  TORCH_CHECK(late_n.numel() >= 1, "late_n must hold the cursor");
+  int64_t* vp = nullptr;
+  if (need_vals) {
+    TORCH_CHECK(late_vals.has_value(), "late tracking needs late_vals");
+    check_dev(*late_vals, torch::kInt64, "late_vals");
+    TORCH_CHECK(late_vals->numel() >= cap,
+                "late_vals smaller than late_keys");
+    vp = late_vals->data_ptr<int64_t>();
+  }
+  return LateSink{late_cutoff, late_keys.data_ptr<int32_t>(),
+                  late_ts.data_ptr<int64_t>(), vp,
+                  late_n.data_ptr<int32_t>(), cap};
+}
+
+static void window_agg_insert_impl(
     torch::Tensor keys,
     torch::Tensor ts,
     c10::optional<torch::Tensor> vals,
@@ -2764,7 +2987,10 @@ void window_agg_insert(
     bool dedup,
     int64_t ts_base,
     int64_t region_bits,
-    int64_t off_ms) {
+    int64_t off_ms,
+    const LateSink* late) {
+  TORCH_CHECK(late == nullptr || !dedup,
+              "late tracking is incompatible with the dedup path");
   if (off_ms <= 0) off_ms = len_ms;
   TORCH_CHECK(off_ms <= len_ms, "window offset must be <= length");
   TORCH_CHECK(off_ms == len_ms || !dedup,
@@ -2801,11 +3027,18 @@ void window_agg_insert(
         (uint64_t)(nslots - 1), align_ms, len_ms, off_ms, ts_base,
         (int)region_bits,
         (unsigned long long*)max_ts.data_ptr<int64_t>(),
-        error_flag.data_ptr<int32_t>(), (const int64_t*)nullptr);
+        error_flag.data_ptr<int32_t>(), (const int64_t*)nullptr,
+        late ? late->cutoff : (int64_t)0, late ? late->keys : nullptr,
+        late ? late->ts : nullptr, late ? late->vals : nullptr,
+        late ? late->n : nullptr, late ? late->cap : (int64_t)0);
   };
   auto dispatch = [&](auto tsptr) {
     using TSV = std::remove_const_t<std::remove_pointer_t<decltype(tsptr)>>;
-    if (mode == AGG_COUNT && !dedup)
+    if (late != nullptr && mode == AGG_COUNT)
+      launch((k_window_agg_insert<AGG_COUNT, false, TSV, true>), tsptr);
+    else if (late != nullptr)
+      launch((k_window_agg_insert<AGG_SUM, false, TSV, true>), tsptr);
+    else if (mode == AGG_COUNT && !dedup)
       launch(k_window_agg_insert<AGG_COUNT, false, TSV>, tsptr);
     else if (mode == AGG_COUNT && dedup)
       launch(k_window_agg_insert<AGG_COUNT, true, TSV>, tsptr);
@@ -2818,7 +3051,57 @@ void window_agg_insert(
   else dispatch(ts.data_ptr<int64_t>());
 }
 
-void radix_window_insert(
+void window_agg_insert(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    c10::optional<torch::Tensor> vals,
+    torch::Tensor tkeys,
+    torch::Tensor tvals,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t mode,
+    bool dedup,
+    int64_t ts_base,
+    int64_t region_bits,
+    int64_t off_ms) {
+  window_agg_insert_impl(keys, ts, vals, tkeys, tvals, max_ts, error_flag,
+                         align_ms, len_ms, mode, dedup, ts_base, region_bits,
+                         off_ms, nullptr);
+}
+
+// Late-tracking form of window_agg_insert: events with absolute
+// ts < late_cutoff are appended to (late_keys, late_ts[, late_vals])
+// at the running cursor late_n instead of being folded (see
+// late_append).  late_keys.numel() is the buffer capacity.
+void window_agg_insert_late(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    c10::optional<torch::Tensor> vals,
+    torch::Tensor tkeys,
+    torch::Tensor tvals,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t mode,
+    int64_t ts_base,
+    int64_t region_bits,
+    int64_t off_ms,
+    int64_t late_cutoff,
+    torch::Tensor late_keys,
+    torch::Tensor late_ts,
+    c10::optional<torch::Tensor> late_vals,
+    torch::Tensor late_n) {
+  LateSink sink = make_late_sink(late_cutoff, late_keys, late_ts, late_vals,
+                                 late_n, mode == AGG_SUM);
+  window_agg_insert_impl(keys, ts, vals, tkeys, tvals, max_ts, error_flag,
+                         align_ms, len_ms, mode, false, ts_base, region_bits,
+                         off_ms, &sink);
+}
+
+static void radix_window_insert_impl(
     torch::Tensor keys,
     torch::Tensor ts,
     c10::optional<torch::Tensor> vals,
@@ -2837,9 +3120,10 @@ void radix_window_insert(
     int64_t mode,
     int64_t ts_base,
     int64_t region_bits,
-    int64_t off_ms = 0,  // sliding stride; 0 or == len_ms for tumbling
-    std::vector<int64_t> seg_counts = {},
-    std::vector<int64_t> seg_bases = {}) {
+    int64_t off_ms,  // sliding stride; 0 or == len_ms for tumbling
+    std::vector<int64_t> seg_counts,
+    std::vector<int64_t> seg_bases,
+    const LateSink* late) {
   if (off_ms <= 0) off_ms = len_ms;
   TORCH_CHECK(off_ms <= len_ms, "window offset must be <= length");
   check_dev(keys, torch::kInt32, "keys");
@@ -2883,6 +3167,9 @@ void radix_window_insert(
   int64_t xf = off_ms < len_ms ? (len_ms + off_ms - 1) / off_ms : 1;
   TORCH_CHECK(xf <= 64, "sliding expansion > 64x; use a larger offset");
   if (kind == SCAT_DIRECT && xf > 1) kind = SCAT_FIXED;
+  // Late tracking lives in the fixed and staged kernels only: the
+  // direct variant routes to fixed, staged2 to staged.
+  if (late != nullptr && kind == SCAT_DIRECT) kind = SCAT_FIXED;
   int coarse = scatter_coarse_bits(kind);
   int seg_bits = (int)region_bits + coarse;
   int64_t nseg = nslots >> seg_bits;
@@ -2891,8 +3178,13 @@ void radix_window_insert(
   size_t staged_lds = (size_t)nseg * SC_GRAN * 8 *
                           (mode == AGG_SUM ? 2 : 1) +
                       4 * (size_t)nseg * sizeof(int);
+  // The LATE staged scatter holds two more ints of (static) LDS; at
+  // nseg == 2048 the COUNT staging alone fills the 160 KiB of a CU, so
+  // late tracking takes the fixed layout there.
+  const size_t late_lds = late != nullptr ? 2 * sizeof(int) : 0;
   while (kind == SCAT_STAGED &&
-         (nseg < 1 || staged_lds > 160 * 1024 || seg_bits > 13)) {
+         (nseg < 1 || staged_lds + late_lds > 160 * 1024 ||
+          seg_bits > 13)) {
     if (coarse > 0 && seg_bits > 13) {
       coarse -= 1;
     } else {
@@ -2959,8 +3251,10 @@ void radix_window_insert(
   uint64_t win_m2, win_maxfast;
   magic_div_u64(off_ms, &win_m2, &win_maxfast);
   unsigned scat_threads = 256;
+  // `extra`: the trailing late-tracking arguments of the staged and
+  // fixed kernels.
   auto scat = [&](auto kern, auto tsptr, const Seg& sg, unsigned gx,
-                  size_t lds) {
+                  size_t lds, auto... extra) {
     hipLaunchKernelGGL(
         kern, dim3(gx), dim3(scat_threads), lds, stream,
         keys.data_ptr<int32_t>() + sg.off, tsptr + sg.off,
@@ -2973,10 +3267,50 @@ void radix_window_insert(
         mode == AGG_SUM ? ov_vals.data_ptr<int64_t>() : nullptr,
         ov_packed.numel(),
         (unsigned long long*)max_ts.data_ptr<int64_t>(),
-        error_flag.data_ptr<int32_t>(), win_m2, win_maxfast);
+        error_flag.data_ptr<int32_t>(), win_m2, win_maxfast, extra...);
+    // A refused launch (LDS budget, bad configuration) must not pass
+    // for an empty batch.
+    HIP_CHECK(hipGetLastError());
+  };
+  // Late-tracking launches: one configuration per mode (the defaults
+  // of the plain path: 512x16 tiles for COUNT, 256x16 for SUM), no
+  // env-tuned U/BLK matrix.
+  auto scat_late = [&](auto tsptr, const Seg& sg) {
+    using TSV = std::remove_const_t<std::remove_pointer_t<decltype(tsptr)>>;
+    if (kind == SCAT_STAGED) {
+      int sthreads = mode == AGG_COUNT ? 512 : 256;
+      scat_threads = (unsigned)sthreads;
+      unsigned gs =
+          (unsigned)((sg.n * xf + sthreads * 16 - 1) / (sthreads * 16));
+      if (gs > 1024u) gs = 1024u;
+      if (gs < 1) gs = 1;
+      if (mode == AGG_COUNT)
+        scat((k_radix_scatter_staged<AGG_COUNT, TSV, 16, 512, true>), tsptr,
+             sg, gs, staged_lds, late->cutoff, late->keys, late->ts,
+             late->vals, late->n, late->cap);
+      else
+        scat((k_radix_scatter_staged<AGG_SUM, TSV, 16, 256, true>), tsptr,
+             sg, gs, staged_lds, late->cutoff, late->keys, late->ts,
+             late->vals, late->n, late->cap);
+    } else {
+      scat_threads = 256;
+      unsigned gx = (unsigned)n_blocks(sg.n, 256);
+      if (mode == AGG_COUNT)
+        scat((k_radix_scatter_fixed<AGG_COUNT, TSV, true>), tsptr, sg, gx,
+             2 * hist_lds, late->cutoff, late->keys, late->ts, late->vals,
+             late->n, late->cap);
+      else
+        scat((k_radix_scatter_fixed<AGG_SUM, TSV, true>), tsptr, sg, gx,
+             2 * hist_lds, late->cutoff, late->keys, late->ts, late->vals,
+             late->n, late->cap);
+    }
   };
   auto scat_any = [&](auto tsptr, const Seg& sg) {
     using TSV = std::remove_const_t<std::remove_pointer_t<decltype(tsptr)>>;
+    if (late != nullptr) {
+      scat_late(tsptr, sg);
+      return;
+    }
     unsigned gx = (unsigned)n_blocks(sg.n, 256);
     if (env_blocks > 0 && (unsigned)env_blocks < gx) gx = (unsigned)env_blocks;
     if (kind == SCAT_STAGED) {
@@ -3014,23 +3348,23 @@ void radix_window_insert(
       } else if (mode == AGG_COUNT) {
         if (sthreads == 512)
           scat((k_radix_scatter_staged<AGG_COUNT, TSV, 16, 512>), tsptr,
-               sg, gs, staged_lds);
+               sg, gs, staged_lds, NO_LATE_ARGS);
         else if (sthreads == 1024)
           scat((k_radix_scatter_staged<AGG_COUNT, TSV, 16, 1024>), tsptr,
-               sg, gs, staged_lds);
+               sg, gs, staged_lds, NO_LATE_ARGS);
         else if (su == 8)
           scat(k_radix_scatter_staged<AGG_COUNT, TSV, 8>, tsptr, sg, gs,
-               staged_lds);
+               staged_lds, NO_LATE_ARGS);
         else if (su == 32)
           scat(k_radix_scatter_staged<AGG_COUNT, TSV, 32>, tsptr, sg, gs,
-               staged_lds);
+               staged_lds, NO_LATE_ARGS);
         else
           scat(k_radix_scatter_staged<AGG_COUNT, TSV, 16>, tsptr, sg, gs,
-               staged_lds);
+               staged_lds, NO_LATE_ARGS);
       } else {
         scat_threads = 256;
         scat(k_radix_scatter_staged<AGG_SUM, TSV>, tsptr, sg, gs,
-             staged_lds);
+             staged_lds, NO_LATE_ARGS);
       }
     } else if (kind == SCAT_DIRECT) {
       scat_threads = 256;
@@ -3042,10 +3376,10 @@ void radix_window_insert(
       scat_threads = 256;
       if (mode == AGG_COUNT)
         scat(k_radix_scatter_fixed<AGG_COUNT, TSV>, tsptr, sg, gx,
-             2 * hist_lds);
+             2 * hist_lds, NO_LATE_ARGS);
       else
         scat(k_radix_scatter_fixed<AGG_SUM, TSV>, tsptr, sg, gx,
-             2 * hist_lds);
+             2 * hist_lds, NO_LATE_ARGS);
     }
   };
   for (const Seg& sg : segs) {
@@ -3081,6 +3415,70 @@ void radix_window_insert(
   };
   if (mode == AGG_COUNT) ov(k_overflow_agg<AGG_COUNT>);
   else ov(k_overflow_agg<AGG_SUM>);
+}
+
+void radix_window_insert(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    c10::optional<torch::Tensor> vals,
+    torch::Tensor tkeys,
+    torch::Tensor tvals,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    torch::Tensor gcursors,
+    torch::Tensor ev_packed,
+    torch::Tensor ev_vals,
+    torch::Tensor ov_cursor,
+    torch::Tensor ov_packed,
+    torch::Tensor ov_vals,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t mode,
+    int64_t ts_base,
+    int64_t region_bits,
+    int64_t off_ms = 0,  // sliding stride; 0 or == len_ms for tumbling
+    std::vector<int64_t> seg_counts = {},
+    std::vector<int64_t> seg_bases = {}) {
+  radix_window_insert_impl(
+      keys, ts, vals, tkeys, tvals, max_ts, error_flag, gcursors, ev_packed,
+      ev_vals, ov_cursor, ov_packed, ov_vals, align_ms, len_ms, mode, ts_base,
+      region_bits, off_ms, std::move(seg_counts), std::move(seg_bases),
+      nullptr);
+}
+
+// Late-tracking form of radix_window_insert (unsegmented batches
+// only; see window_agg_insert_late for the late arguments).
+void radix_window_insert_late(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    c10::optional<torch::Tensor> vals,
+    torch::Tensor tkeys,
+    torch::Tensor tvals,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    torch::Tensor gcursors,
+    torch::Tensor ev_packed,
+    torch::Tensor ev_vals,
+    torch::Tensor ov_cursor,
+    torch::Tensor ov_packed,
+    torch::Tensor ov_vals,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t mode,
+    int64_t ts_base,
+    int64_t region_bits,
+    int64_t off_ms,
+    int64_t late_cutoff,
+    torch::Tensor late_keys,
+    torch::Tensor late_ts,
+    c10::optional<torch::Tensor> late_vals,
+    torch::Tensor late_n) {
+  LateSink sink = make_late_sink(late_cutoff, late_keys, late_ts, late_vals,
+                                 late_n, mode == AGG_SUM);
+  radix_window_insert_impl(
+      keys, ts, vals, tkeys, tvals, max_ts, error_flag, gcursors, ev_packed,
+      ev_vals, ov_cursor, ov_packed, ov_vals, align_ms, len_ms, mode, ts_base,
+      region_bits, off_ms, {}, {}, &sink);
 }
 
 // Split radix insert for the per-step Python engine's pipelined
@@ -3203,8 +3601,10 @@ void radix_scatter_only(
     segs.push_back({0, n, ts_base});
   }
   unsigned scat_threads = 256;
+  // `extra`: the trailing late-tracking arguments of the staged and
+  // fixed kernels (always off on this path).
   auto scat = [&](auto kern, auto tsptr, const Seg& sg, unsigned gx,
-                  size_t lds) {
+                  size_t lds, auto... extra) {
     hipLaunchKernelGGL(
         kern, dim3(gx), dim3(scat_threads), lds,
         stream, keys.data_ptr<int32_t>() + sg.off, tsptr + sg.off,
@@ -3217,7 +3617,7 @@ void radix_scatter_only(
         mode == AGG_SUM ? ov_vals.data_ptr<int64_t>() : nullptr,
         ov_packed.numel(),
         (unsigned long long*)max_ts.data_ptr<int64_t>(),
-        error_flag.data_ptr<int32_t>(), win_m2, win_maxfast);
+        error_flag.data_ptr<int32_t>(), win_m2, win_maxfast, extra...);
   };
   auto scat_any = [&](auto tsptr, const Seg& sg) {
     using TSV = std::remove_const_t<std::remove_pointer_t<decltype(tsptr)>>;
@@ -3229,14 +3629,14 @@ void radix_scatter_only(
         if (gs < 1) gs = 1;
         scat_threads = 512;
         scat((k_radix_scatter_staged<AGG_COUNT, TSV, 16, 512>), tsptr,
-             sg, gs, staged_lds);
+             sg, gs, staged_lds, NO_LATE_ARGS);
         scat_threads = 256;
       } else {
         unsigned gs = (unsigned)((sg.n + 4095) / 4096);
         if (gs > 1024) gs = 1024;
         if (gs < 1) gs = 1;
         scat(k_radix_scatter_staged<AGG_SUM, TSV>, tsptr, sg, gs,
-             staged_lds);
+             staged_lds, NO_LATE_ARGS);
       }
     } else if (kind == SCAT_DIRECT) {
       unsigned gx = (unsigned)n_blocks(sg.n, 256);
@@ -3248,10 +3648,10 @@ void radix_scatter_only(
       unsigned gx = (unsigned)n_blocks(sg.n, 256);
       if (mode == AGG_COUNT)
         scat(k_radix_scatter_fixed<AGG_COUNT, TSV>, tsptr, sg, gx,
-             2 * hist_lds);
+             2 * hist_lds, NO_LATE_ARGS);
       else
         scat(k_radix_scatter_fixed<AGG_SUM, TSV>, tsptr, sg, gx,
-             2 * hist_lds);
+             2 * hist_lds, NO_LATE_ARGS);
     }
   };
   for (const Seg& sg : segs) {
@@ -3447,6 +3847,52 @@ void close_migrate(
       out_keys.numel(), error_flag.data_ptr<int32_t>());
 }
 
+static void stats_insert_impl(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    torch::Tensor vals,
+    torch::Tensor tkeys,
+    torch::Tensor tcnt,
+    torch::Tensor tsum,
+    torch::Tensor tmin,
+    torch::Tensor tmax,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    const LateSink* late) {
+  check_dev(keys, torch::kInt32, "keys");
+  check_dev(ts, torch::kInt64, "ts");
+  check_dev(vals, torch::kInt64, "vals");
+  check_dev(tkeys, torch::kInt64, "tkeys");
+  int64_t n = keys.numel();
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK((nslots & (nslots - 1)) == 0, "table size must be 2^k");
+  if (n == 0) return;
+  auto stream = at::hip::getCurrentHIPStream();
+  dim3 block(256);
+  dim3 grid(n_blocks(n, 256));
+  auto launch = [&](auto kern, auto... extra) {
+    hipLaunchKernelGGL(
+        kern, grid, block, 0, stream, keys.data_ptr<int32_t>(),
+        ts.data_ptr<int64_t>(), vals.data_ptr<int64_t>(),
+        n, (uint64_t*)tkeys.data_ptr<int64_t>(),
+        (long long*)tcnt.data_ptr<int64_t>(),
+        (long long*)tsum.data_ptr<int64_t>(),
+        (long long*)tmin.data_ptr<int64_t>(),
+        (long long*)tmax.data_ptr<int64_t>(), (uint64_t)(nslots - 1),
+        align_ms, len_ms, ts_base,
+        (unsigned long long*)max_ts.data_ptr<int64_t>(),
+        error_flag.data_ptr<int32_t>(), extra...);
+  };
+  if (late != nullptr)
+    launch(k_stats_insert<true>, late->cutoff, late->keys, late->ts,
+           late->vals, late->n, late->cap);
+  else
+    launch(k_stats_insert<false>, NO_LATE_ARGS);
+}
+
 void stats_insert(
     torch::Tensor keys,
     torch::Tensor ts,
@@ -3461,31 +3907,38 @@ void stats_insert(
     int64_t align_ms,
     int64_t len_ms,
     int64_t ts_base) {
-  check_dev(keys, torch::kInt32, "keys");
-  check_dev(ts, torch::kInt64, "ts");
-  check_dev(vals, torch::kInt64, "vals");
-  check_dev(tkeys, torch::kInt64, "tkeys");
-  int64_t n = keys.numel();
-  int64_t nslots = tkeys.numel();
-  TORCH_CHECK((nslots & (nslots - 1)) == 0, "table size must be 2^k");
-  if (n == 0) return;
-  auto stream = at::hip::getCurrentHIPStream();
-  dim3 block(256);
-  dim3 grid(n_blocks(n, 256));
-  hipLaunchKernelGGL(
-      k_stats_insert, grid, block, 0, stream, keys.data_ptr<int32_t>(),
-      ts.data_ptr<int64_t>(), vals.data_ptr<int64_t>(),
-      n, (uint64_t*)tkeys.data_ptr<int64_t>(),
-      (long long*)tcnt.data_ptr<int64_t>(),
-      (long long*)tsum.data_ptr<int64_t>(),
-      (long long*)tmin.data_ptr<int64_t>(),
-      (long long*)tmax.data_ptr<int64_t>(), (uint64_t)(nslots - 1),
-      align_ms, len_ms, ts_base,
-      (unsigned long long*)max_ts.data_ptr<int64_t>(),
-      error_flag.data_ptr<int32_t>());
+  stats_insert_impl(keys, ts, vals, tkeys, tcnt, tsum, tmin, tmax, max_ts,
+                    error_flag, align_ms, len_ms, ts_base, nullptr);
 }
 
-void radix_stats_insert(
+// Late-tracking form of stats_insert (see window_agg_insert_late).
+void stats_insert_late(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    torch::Tensor vals,
+    torch::Tensor tkeys,
+    torch::Tensor tcnt,
+    torch::Tensor tsum,
+    torch::Tensor tmin,
+    torch::Tensor tmax,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    int64_t late_cutoff,
+    torch::Tensor late_keys,
+    torch::Tensor late_ts,
+    torch::Tensor late_vals,
+    torch::Tensor late_n) {
+  c10::optional<torch::Tensor> lv(late_vals);
+  LateSink sink =
+      make_late_sink(late_cutoff, late_keys, late_ts, lv, late_n, true);
+  stats_insert_impl(keys, ts, vals, tkeys, tcnt, tsum, tmin, tmax, max_ts,
+                    error_flag, align_ms, len_ms, ts_base, &sink);
+}
+
+static void radix_stats_insert_impl(
     torch::Tensor keys,
     torch::Tensor ts,
     torch::Tensor vals,
@@ -3505,7 +3958,8 @@ void radix_stats_insert(
     int64_t align_ms,
     int64_t len_ms,
     int64_t ts_base,
-    int64_t region_bits) {
+    int64_t region_bits,
+    const LateSink* late) {
   check_dev(keys, torch::kInt32, "keys");
   bool ts32 = ts.scalar_type() == torch::kInt32;
   if (!ts32) check_dev(ts, torch::kInt64, "ts");
@@ -3526,13 +3980,18 @@ void radix_stats_insert(
   // Same scatter-variant decision as the window path; the stats agg
   // stages 40 B/LDS slot, capping coarse segments at lds_bits 11.
   ScatterKind kind = scatter_kind_env();
+  // Late tracking lives in the fixed and staged kernels only.
+  if (late != nullptr && kind == SCAT_DIRECT) kind = SCAT_FIXED;
   int coarse = scatter_coarse_bits(kind);
   int seg_bits = (int)region_bits + coarse;
   int64_t nseg = nslots >> seg_bits;
   size_t staged_lds = (size_t)nseg * SC_GRAN * 8 * 2 +
                       4 * (size_t)nseg * sizeof(int);
+  // Two more ints of static LDS in the LATE staged scatter.
+  const size_t late_lds = late != nullptr ? 2 * sizeof(int) : 0;
   while (kind == SCAT_STAGED &&
-         (nseg < 1 || staged_lds > 160 * 1024 || seg_bits > 11)) {
+         (nseg < 1 || staged_lds + late_lds > 160 * 1024 ||
+          seg_bits > 11)) {
     if (coarse > 0 && seg_bits > 11) {
       coarse -= 1;
     } else {
@@ -3574,8 +4033,9 @@ void radix_stats_insert(
       unsigned gs = (unsigned)((n + 8191) / 8192);
       if (gs > 1024) gs = 1024;
       if (gs < 1) gs = 1;
+      auto staged = [&](auto kern, auto... extra) {
       hipLaunchKernelGGL(
-          (k_radix_scatter_staged<AGG_SUM, TSV, 16, 512>), dim3(gs),
+          kern, dim3(gs),
           dim3(512), staged_lds,
           stream, keys.data_ptr<int32_t>(), tsptr,
           vals.data_ptr<int64_t>(), n, align_ms, len_ms, len_ms, ts_base,
@@ -3586,10 +4046,19 @@ void radix_stats_insert(
           (uint64_t*)ov_packed.data_ptr<int64_t>(),
           ov_vals.data_ptr<int64_t>(), ov_packed.numel(),
           (unsigned long long*)max_ts.data_ptr<int64_t>(),
-          error_flag.data_ptr<int32_t>(), win_m2, win_maxfast);
+          error_flag.data_ptr<int32_t>(), win_m2, win_maxfast, extra...);
+      };
+      if (late != nullptr)
+        staged((k_radix_scatter_staged<AGG_SUM, TSV, 16, 512, true>),
+               late->cutoff, late->keys, late->ts, late->vals, late->n,
+               late->cap);
+      else
+        staged((k_radix_scatter_staged<AGG_SUM, TSV, 16, 512>),
+               NO_LATE_ARGS);
     } else {
+      auto fixed = [&](auto kern, auto... extra) {
       hipLaunchKernelGGL(
-          (k_radix_scatter_fixed<AGG_SUM, TSV>), grid, block,
+          kern, grid, block,
           2 * hist_lds, stream,
           keys.data_ptr<int32_t>(), tsptr,
           vals.data_ptr<int64_t>(), n, align_ms, len_ms, len_ms, ts_base,
@@ -3600,11 +4069,18 @@ void radix_stats_insert(
           (uint64_t*)ov_packed.data_ptr<int64_t>(), ov_vals.data_ptr<int64_t>(),
           ov_packed.numel(),
           (unsigned long long*)max_ts.data_ptr<int64_t>(),
-          error_flag.data_ptr<int32_t>(), win_m2, win_maxfast);
+          error_flag.data_ptr<int32_t>(), win_m2, win_maxfast, extra...);
+      };
+      if (late != nullptr)
+        fixed((k_radix_scatter_fixed<AGG_SUM, TSV, true>), late->cutoff,
+              late->keys, late->ts, late->vals, late->n, late->cap);
+      else
+        fixed((k_radix_scatter_fixed<AGG_SUM, TSV>), NO_LATE_ARGS);
     }
   };
   if (ts32) scat_any(ts.data_ptr<int32_t>());
   else scat_any(ts.data_ptr<int64_t>());
+  HIP_CHECK(hipGetLastError());
 
   auto offsets = at::arange(
       nseg, at::TensorOptions().dtype(at::kInt).device(keys.device()));
@@ -3632,6 +4108,69 @@ void radix_stats_insert(
       (long long*)tmin.data_ptr<int64_t>(),
       (long long*)tmax.data_ptr<int64_t>(), mask,
       error_flag.data_ptr<int32_t>());
+}
+
+void radix_stats_insert(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    torch::Tensor vals,
+    torch::Tensor tkeys,
+    torch::Tensor tcnt,
+    torch::Tensor tsum,
+    torch::Tensor tmin,
+    torch::Tensor tmax,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    torch::Tensor gcursors,
+    torch::Tensor ev_packed,
+    torch::Tensor ev_vals,
+    torch::Tensor ov_cursor,
+    torch::Tensor ov_packed,
+    torch::Tensor ov_vals,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    int64_t region_bits) {
+  radix_stats_insert_impl(
+      keys, ts, vals, tkeys, tcnt, tsum, tmin, tmax, max_ts, error_flag,
+      gcursors, ev_packed, ev_vals, ov_cursor, ov_packed, ov_vals, align_ms,
+      len_ms, ts_base, region_bits, nullptr);
+}
+
+// Late-tracking form of radix_stats_insert (see window_agg_insert_late).
+void radix_stats_insert_late(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    torch::Tensor vals,
+    torch::Tensor tkeys,
+    torch::Tensor tcnt,
+    torch::Tensor tsum,
+    torch::Tensor tmin,
+    torch::Tensor tmax,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    torch::Tensor gcursors,
+    torch::Tensor ev_packed,
+    torch::Tensor ev_vals,
+    torch::Tensor ov_cursor,
+    torch::Tensor ov_packed,
+    torch::Tensor ov_vals,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    int64_t region_bits,
+    int64_t late_cutoff,
+    torch::Tensor late_keys,
+    torch::Tensor late_ts,
+    torch::Tensor late_vals,
+    torch::Tensor late_n) {
+  c10::optional<torch::Tensor> lv(late_vals);
+  LateSink sink =
+      make_late_sink(late_cutoff, late_keys, late_ts, lv, late_n, true);
+  radix_stats_insert_impl(
+      keys, ts, vals, tkeys, tcnt, tsum, tmin, tmax, max_ts, error_flag,
+      gcursors, ev_packed, ev_vals, ov_cursor, ov_packed, ov_vals, align_ms,
+      len_ms, ts_base, region_bits, &sink);
 }
 
 void stats_fixup(
@@ -3817,7 +4356,8 @@ void radix_join_insert(
         (uint64_t*)ov_packed.data_ptr<int64_t>(), ov_vals.data_ptr<int64_t>(),
         ov_packed.numel(),
         (unsigned long long*)max_ts_scratch.data_ptr<int64_t>(),
-        error_flag.data_ptr<int32_t>(), (uint64_t)1 << 24, ~(uint64_t)0);
+        error_flag.data_ptr<int32_t>(), (uint64_t)1 << 24, ~(uint64_t)0,
+        NO_LATE_ARGS);
   } else {
     hipLaunchKernelGGL(
         k_radix_scatter_fixed<AGG_SUM>, grid, block, 2 * hist_lds, stream,
@@ -3830,7 +4370,8 @@ void radix_join_insert(
         (uint64_t*)ov_packed.data_ptr<int64_t>(), ov_vals.data_ptr<int64_t>(),
         ov_packed.numel(),
         (unsigned long long*)max_ts_scratch.data_ptr<int64_t>(),
-        error_flag.data_ptr<int32_t>(), (uint64_t)1 << 24, ~(uint64_t)0);
+        error_flag.data_ptr<int32_t>(), (uint64_t)1 << 24, ~(uint64_t)0,
+        NO_LATE_ARGS);
   }
   // LDS staging sized one bit above the segment's table span
   // (2^seg_bits cells per segment); headroom keeps the in-LDS probe
@@ -3928,7 +4469,7 @@ __global__ void k_session_merge_batch(
     uint64_t key = (uint64_t)(uint32_t)keys[i];
     uint64_t slot = session_find_or_claim(skeys, mask, key);
     if (slot == ~0ULL) {
-      atomicExch(error_flag, 1);
+      atomicOr(error_flag, 1);
       continue;
     }
     long long lo = mn_ts[i] + ts_shift;
@@ -3944,7 +4485,7 @@ __global__ void k_session_merge_batch(
         out_end[idx] = last;
         out_vals[idx] = sacc[slot];
       } else {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       }
       last = -1;
     }
@@ -3983,7 +4524,7 @@ __global__ void k_session_restore(
     uint64_t slot = session_find_or_claim(
         skeys, mask, (uint64_t)(uint32_t)keys[i]);
     if (slot == ~0ULL) {
-      atomicExch(error_flag, 1);
+      atomicOr(error_flag, 1);
       continue;
     }
     sstart[slot] = start[i];
@@ -4009,7 +4550,7 @@ __device__ inline void session_merge_cell(
     int64_t* out_vals, int* out_n, int64_t out_cap, int* error_flag) {
   uint64_t slot = session_find_or_claim(skeys, mask, key);
   if (slot == ~0ULL) {
-    atomicExch(error_flag, 1);
+    atomicOr(error_flag, 1);
     return;
   }
   long long last = slast[slot];
@@ -4021,7 +4562,7 @@ __device__ inline void session_merge_cell(
       out_end[idx] = last;
       out_vals[idx] = sacc[slot];
     } else {
-      atomicExch(error_flag, 1);
+      atomicOr(error_flag, 1);
     }
     last = -1;
   }
@@ -4107,7 +4648,7 @@ __global__ __launch_bounds__(1024) void k_radix_session_agg(
         ov_packed[opos] = key;
         ov_vals[opos] = t;
       } else {
-        atomicExch(error_flag, 1);
+        atomicOr(error_flag, 1);
       }
     }
   }
@@ -4781,7 +5322,8 @@ int64_t native_run_window_steps(
                   (uint64_t*)ovp.data_ptr<int64_t>(), (int64_t*)nullptr,
                   ovp.numel(),
                   (unsigned long long*)max_ts.data_ptr<int64_t>(),
-                  error_flag.data_ptr<int32_t>(), win_m2, win_maxfast);
+                  error_flag.data_ptr<int32_t>(), win_m2, win_maxfast,
+                  NO_LATE_ARGS);
             };
             if (su == 8)
               launch_staged(k_radix_scatter_staged<AGG_COUNT, TSV, 8>);
@@ -4814,7 +5356,8 @@ int64_t native_run_window_steps(
                 ovc.data_ptr<int32_t>(), (uint64_t*)ovp.data_ptr<int64_t>(),
                 (int64_t*)nullptr, ovp.numel(),
                 (unsigned long long*)max_ts.data_ptr<int64_t>(),
-                error_flag.data_ptr<int32_t>(), win_m2, win_maxfast);
+                error_flag.data_ptr<int32_t>(), win_m2, win_maxfast,
+                NO_LATE_ARGS);
           }
         };
         if (ts.scalar_type() == torch::kInt32)
@@ -4854,7 +5397,8 @@ int64_t native_run_window_steps(
               (uint64_t)(nslots - 1), align_ms, len_ms, len_ms, base,
               (int)region_bits,
               (unsigned long long*)max_ts.data_ptr<int64_t>(),
-              error_flag.data_ptr<int32_t>(), (const int64_t*)nullptr);
+              error_flag.data_ptr<int32_t>(), (const int64_t*)nullptr,
+              NO_LATE_ARGS);
         };
         auto disp = [&](auto tsptr) {
           using TSV =
@@ -4969,7 +5513,7 @@ int64_t native_run_window_steps_graph(
         len_ms, len_ms, 0, (int)region_bits,
         (unsigned long long*)max_ts.data_ptr<int64_t>(),
         error_flag.data_ptr<int32_t>(),
-        (const int64_t*)ts_base_dev.data_ptr<int64_t>());
+        (const int64_t*)ts_base_dev.data_ptr<int64_t>(), NO_LATE_ARGS);
     hipLaunchKernelGGL(
         k_bump, dim3(1), dim3(1), 0, st,
         ts_base_dev.data_ptr<int64_t>(), sim_ms_per_batch);
@@ -5140,7 +5684,7 @@ void session_radix_insert(
         (uint64_t*)ov_packed.data_ptr<int64_t>(),
         ov_vals.data_ptr<int64_t>(), ov_packed.numel(),
         (unsigned long long*)max_ts.data_ptr<int64_t>(),
-        error_flag.data_ptr<int32_t>(), win_m2, win_maxfast);
+        error_flag.data_ptr<int32_t>(), win_m2, win_maxfast, NO_LATE_ARGS);
   };
   auto scat = [&](auto kern, auto tsptr, unsigned gx, size_t lds) {
     hipLaunchKernelGGL(
@@ -5153,7 +5697,7 @@ void session_radix_insert(
         (uint64_t*)ov_packed.data_ptr<int64_t>(),
         ov_vals.data_ptr<int64_t>(), ov_packed.numel(),
         (unsigned long long*)max_ts.data_ptr<int64_t>(),
-        error_flag.data_ptr<int32_t>(), win_m2, win_maxfast);
+        error_flag.data_ptr<int32_t>(), win_m2, win_maxfast, NO_LATE_ARGS);
   };
   auto scat_any = [&](auto tsptr) {
     using TSV = std::remove_const_t<std::remove_pointer_t<decltype(tsptr)>>;
@@ -5362,6 +5906,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Scatter stage of the radix insert on the current stream");
   m.def("radix_agg_only", &radix_agg_only,
         "Aggregation stage of the radix insert on the current stream");
+  m.def("window_agg_insert_late", &window_agg_insert_late,
+        "Single-pass window insert that diverts events below the late "
+        "cutoff to a late buffer");
+  m.def("radix_window_insert_late", &radix_window_insert_late,
+        "Radix window insert that diverts events below the late cutoff "
+        "to a late buffer");
+  m.def("stats_insert_late", &stats_insert_late,
+        "Stats insert that diverts events below the late cutoff to a "
+        "late buffer");
+  m.def("radix_stats_insert_late", &radix_stats_insert_late,
+        "Radix stats insert that diverts events below the late cutoff "
+        "to a late buffer");
   m.def("radix_window_insert", &radix_window_insert,
         "Radix-partitioned LDS-staged keyed window aggregation");
   m.def("close_migrate", &close_migrate,

@@ -253,6 +253,204 @@ class _LazyTsBatch:
         )
 
 
+#: `error_flag` bit set by the late-tracking insert kernels when a late
+#: row would land past the late buffer (ERR_LATE_OVERFLOW in
+#: stream_kernels.hip); every other bit means a table overflow.
+ERR_LATE_OVERFLOW = 2
+
+
+def _check_error_flag(flag: int, what: str) -> None:
+    if flag & ERR_LATE_OVERFLOW:
+        msg = (
+            "late-event buffer overflowed on device (late rows were "
+            "dropped); this is a bug in the host-side drain bound"
+        )
+        raise RuntimeError(msg)
+    if flag != 0:
+        msg = f"{what} overflowed; increase slots_pow"
+        raise RuntimeError(msg)
+
+
+class _LateTracker:
+    """Late-event bookkeeping shared by :class:`WindowAggState` and
+    `StatsAggState` under ``track_late=True``.
+
+    The insert kernels append `(key, absolute ts[, val])` of every
+    event below the cutoff at a device cursor that is never reset by
+    an insert, so a well-ordered stream costs no host synchronisation.
+    The host only keeps an upper bound on the undrained rows (the sum
+    of the batch lengths inserted since the last drain) and drains
+    into a carry list before that bound could exceed the buffer.
+
+    The buffer defaults to `_LATE_BATCHES` times the largest batch, and
+    the bound is tightened without synchronising: once it passes half
+    the buffer, the cursor is copied to pinned memory asynchronously
+    after an insert, and once that copy has landed the undrained rows
+    are at most its value plus the batches inserted since.  On an ordered stream the cursor stays 0,
+    so the bound never reaches the buffer unless the host runs more
+    than `_LATE_BATCHES - 1` batches ahead of the device.
+    """
+
+    _LATE_BATCHES = 4
+
+    def __init__(self, device, wait_ms: int, has_vals: bool, late_cap: int = 0):
+        self.device = device
+        self.cpu = device.type == "cpu"
+        self.wait_ms = wait_ms
+        self.has_vals = has_vals
+        self.min_cap = late_cap
+        self.cap = 0
+        self.keys = None
+        self.ts = None
+        self.vals = None
+        self.n = None  # device cursor, int32 [1]
+        self.bound = 0  # upper bound on undrained device rows
+        self.pending: list = []  # CPU twin of the device buffer
+        self.carry: list = []  # drained (keys, ts, vals) chunks
+        # Asynchronous cursor readback: (event, pinned int32 [1]) while
+        # in flight, and the batch lengths reserved since it was taken.
+        self._probe = None
+        self._probe_pin = None
+        self._since_probe = 0
+
+    def reserve(self, n_batch: int, error_flag) -> None:
+        """Make room for a batch that may be entirely late."""
+        import torch
+
+        # An empty batch still allocates (the kernels want the buffers).
+        n_batch = max(n_batch, 1)
+        self._refine()
+        self._since_probe += n_batch
+        if n_batch > self.cap:
+            # Lazily allocated; grows with the largest batch.
+            if self.bound:
+                self.drain(error_flag)
+            self.cap = max(
+                n_batch,
+                self.min_cap if self.min_cap else self._LATE_BATCHES * n_batch,
+                1,
+            )
+            if self.cpu:
+                self.bound += n_batch
+                return
+            self.keys = torch.empty(
+                self.cap, dtype=torch.int32, device=self.device
+            )
+            self.ts = torch.empty(
+                self.cap, dtype=torch.int64, device=self.device
+            )
+            self.vals = (
+                torch.empty(self.cap, dtype=torch.int64, device=self.device)
+                if self.has_vals
+                else None
+            )
+            if self.n is None:
+                self.n = torch.zeros(1, dtype=torch.int32, device=self.device)
+        elif self.bound + n_batch > self.cap:
+            self.drain(error_flag)
+        self.bound += n_batch
+
+    def _refine(self) -> None:
+        """Tighten the bound from a landed cursor copy (never waits).
+        A copy taken before a drain still bounds the rows after it:
+        those come from batches inserted since the copy."""
+        if self._probe is not None and self._probe[0].query():
+            seen = int(self._probe[1].item())  # pinned host memory
+            self.bound = min(self.bound, seen + self._since_probe)
+            self._probe = None
+
+    def inserted(self) -> None:
+        """Call after an insert was launched: starts the next
+        asynchronous cursor readback unless one is in flight."""
+        import torch
+
+        if self.cpu or self._probe is not None:
+            return
+        if 2 * self.bound <= self.cap:
+            # Far from the buffer: skip the copy (it costs a few
+            # microseconds of stream time per batch).
+            return
+        if self._probe_pin is None:
+            self._probe_pin = torch.zeros(
+                1, dtype=torch.int32, pin_memory=True
+            )
+        self._probe_pin.copy_(self.n, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._probe = (ev, self._probe_pin)
+        self._since_probe = 0
+
+    def drain(self, error_flag) -> None:
+        """Move the device rows into the carry (synchronises)."""
+        if self.cpu:
+            self.carry.extend(self.pending)
+            self.pending = []
+            self.bound = 0
+            return
+        if self.n is None or self.bound == 0:
+            return
+        import torch
+
+        # Cursor and error flag in one readback.
+        n, flag = torch.cat([self.n, error_flag]).tolist()
+        _check_error_flag(flag & ERR_LATE_OVERFLOW, "late buffer")
+        if n > self.cap:
+            msg = f"late cursor {n} past late_cap {self.cap}"
+            raise RuntimeError(msg)
+        if n:
+            self.carry.append(
+                (
+                    self.keys[:n].clone(),
+                    self.ts[:n].clone(),
+                    self.vals[:n].clone() if self.has_vals else None,
+                )
+            )
+            self.n.zero_()
+        self.bound = 0
+
+    def add_host(self, keys, ts, vals) -> None:
+        """CPU twin: append already-split late rows."""
+        if len(keys):
+            self.pending.append((keys, ts, vals if self.has_vals else None))
+
+    def take(self, error_flag) -> Optional["RecordBatch"]:
+        import torch
+
+        self.drain(error_flag)
+        if not self.carry:
+            return None
+        chunks, self.carry = self.carry, []
+        keys = torch.cat([c[0] for c in chunks])
+        ts = torch.cat([c[1] for c in chunks])
+        vals = torch.cat([c[2] for c in chunks]) if self.has_vals else None
+        return RecordBatch(keys, ts, vals)
+
+
+def _split_late_cpu(batch: "RecordBatch", cutoff: int, late: _LateTracker):
+    """CPU-twin rule of the `LATE` kernels: events with absolute
+    ``ts < cutoff`` go to the late rows; returns the accepted rest."""
+    import torch
+
+    late.reserve(len(batch), None)
+    abs_ts = batch.ts.to(torch.int64) + batch.ts_base
+    is_late = abs_ts < cutoff
+    if not bool(is_late.any()):
+        return batch
+    late.add_host(
+        batch.keys[is_late],
+        abs_ts[is_late],
+        batch.vals[is_late] if batch.vals is not None else None,
+    )
+    keep = ~is_late
+    return RecordBatch(
+        batch.keys[keep],
+        batch.ts[keep],
+        batch.vals[keep] if batch.vals is not None else None,
+        max_ts=batch.max_ts,
+        ts_base=batch.ts_base,
+    )
+
+
 class WindowAggState:
     """HBM-resident keyed tumbling-window aggregation state.
 
@@ -274,6 +472,9 @@ class WindowAggState:
         max_batch: int = 0,
         off_ms: int = 0,
         radix_v2: bool = False,
+        track_late: bool = False,
+        wait_ms: int = 0,
+        late_cap: int = 0,
     ):
         """:arg radix: Use the radix-partitioned LDS-staged insert path
         (fastest for high-cardinality keys; requires `max_batch`, the
@@ -281,8 +482,46 @@ class WindowAggState:
         :arg region_bits: log2 of the table-region size when `radix`.
         :arg off_ms: Window stride; 0 or == len_ms for tumbling,
             < len_ms for sliding (single-pass insert path only).
+        :arg track_late: Accept disordered batches and report late
+            events.  The watermark is batch-granular (the max over all
+            EARLIER batches of the event timestamps and the `max_ts`
+            hints); an event with absolute ``ts < watermark -
+            wait_ms`` is late: it joins no window (for sliding, none
+            of the windows it overlaps), does not advance the
+            watermark and is handed out once by :meth:`take_late`.
+            Every other event is accepted however disordered.  The
+            decision is fused into the insert kernels.  Batches that
+            carry `max_ts` stay free of host synchronisation: on the
+            device the hint alone advances the host watermark, so it
+            must be at least the batch's largest timestamp (a lower
+            hint would leave the next cutoff behind the events and
+            accept what the rule calls late; the CPU twin takes the
+            maximum of both).  Without the hint each insert reads the
+            batch maximum back from the device.  Only :meth:`insert` tracks late events: it is
+            incompatible with `dedup`, `radix_v2`, `insert_pipelined`,
+            `insert_lazy`, `native_run` and `native_run_graph`, which
+            stay watermark-ordered.
+        :arg wait_ms: Lateness allowance under `track_late` (pass the
+            same value to :meth:`close_due`).
+        :arg late_cap: Late-buffer capacity in rows (never below the
+            largest batch); by default four times the largest batch.
+            The buffer is allocated lazily and grows with the largest
+            batch.  :meth:`insert` drains it into a host-side carry
+            (one synchronisation) before the rows it may hold could
+            exceed it, so nothing is ever dropped.
         """
         import torch
+
+        if track_late and (dedup or radix_v2):
+            msg = "track_late is incompatible with dedup and radix_v2"
+            raise ValueError(msg)
+        self.track_late = track_late
+        self.wait_ms = wait_ms
+        self._late = (
+            _LateTracker(device, wait_ms, mode == AGG_SUM, late_cap)
+            if track_late
+            else None
+        )
 
         self.device = device
         self.align_ms = align_ms
@@ -364,6 +603,13 @@ class WindowAggState:
     def _insert_cpu(self, batch: RecordBatch) -> None:
         import numpy as np
 
+        if self.track_late:
+            # The rule of the LATE kernels: cutoff from the watermark
+            # of the EARLIER batches; a late event is dropped before
+            # the window computation (so from every sliding window).
+            batch = _split_late_cpu(
+                batch, self.max_ts_host - self.wait_ms, self._late
+            )
         keys = batch.keys.numpy()
         ts64 = batch.ts.numpy().astype("int64", copy=False)
         wins = (
@@ -466,6 +712,9 @@ class WindowAggState:
             self._alloc_rx(int(len(batch) * 5 // 4))
         import torch
 
+        if self.track_late:
+            self._insert_late(batch)
+            return
         if self.radix_v2:
             self.k.radix_v2_window_insert(
                 batch.keys,
@@ -527,6 +776,84 @@ class WindowAggState:
         if batch.max_ts is not None and batch.max_ts > self.max_ts_host:
             self.max_ts_host = batch.max_ts
 
+    def _insert_late(self, batch: RecordBatch) -> None:
+        """Device insert with the late decision fused into the kernels
+        (same launches as :meth:`insert` otherwise)."""
+        lt = self._late
+        lt.reserve(len(batch), self.error_flag)
+        cutoff = self.max_ts_host - self.wait_ms
+        late_args = (cutoff, lt.keys, lt.ts, lt.vals, lt.n)
+        if self.radix:
+            self.k.radix_window_insert_late(
+                batch.keys,
+                batch.ts,
+                batch.vals,
+                self.tkeys,
+                self.tvals,
+                self.max_ts_dev,
+                self.error_flag,
+                self.rx_gcursors,
+                self.rx_packed,
+                self.rx_vals,
+                self.rx_ov_cursor,
+                self.rx_ov_packed,
+                self.rx_ov_vals,
+                self.align_ms,
+                self.len_ms,
+                self.mode,
+                batch.ts_base,
+                self.region_bits,
+                self.off_ms,
+                *late_args,
+            )
+        else:
+            self.k.window_agg_insert_late(
+                batch.keys,
+                batch.ts,
+                batch.vals,
+                self.tkeys,
+                self.tvals,
+                self.max_ts_dev,
+                self.error_flag,
+                self.align_ms,
+                self.len_ms,
+                self.mode,
+                batch.ts_base,
+                self.region_bits,
+                self.off_ms,
+                *late_args,
+            )
+        lt.inserted()
+        if batch.max_ts is not None:
+            if batch.max_ts > self.max_ts_host:
+                self.max_ts_host = batch.max_ts
+        else:
+            # The next cutoff needs this batch's maximum: without the
+            # hint it has to come back from the device.
+            self.watermark_ms(sync=True)
+
+    def take_late(self) -> Optional[RecordBatch]:
+        """Drain the late events accumulated since the last call
+        (`track_late` only): `keys`, absolute int64 `ts` (``ts_base``
+        0) and `vals` (None in COUNT mode), one row per late event.
+        Synchronises with the device.  :meth:`snapshot_to_host` does
+        not hold late rows: drain them first and persist them next to
+        the snapshot, as the windowing lowering does."""
+        if self._late is None:
+            return None
+        return self._late.take(None if self.cpu else self.error_flag)
+
+    def late_drained(self) -> bool:
+        """True when :meth:`insert` had to drain late rows into the
+        host-side carry (the device buffer could have filled): the
+        caller has synchronised already and may as well take them."""
+        return self._late is not None and bool(self._late.carry)
+
+    def _ordered_only(self, what: str) -> None:
+        if self.track_late:
+            msg = f"{what} is watermark-ordered only; track_late needs insert()"
+            raise ValueError(msg)
+
     def _ensure_pipe(self) -> None:
         import torch
 
@@ -584,6 +911,7 @@ class WindowAggState:
         reuse).  ``works`` (async exchange handles) are waited on the
         side stream, so the NCCL completion gates only the scatter —
         not the previous step's aggregation."""
+        self._ordered_only("insert_pipelined")
         import torch
 
         n = int(keys.numel())
@@ -650,6 +978,7 @@ class WindowAggState:
         rebuild (~3 HBM passes over the biggest column per step at
         world > 1).  Other paths materialize first.
         """
+        self._ordered_only("insert_lazy")
         if self.cpu or not self.radix or self.radix_v2:
             self.insert(lz.materialize())
             return
@@ -722,9 +1051,9 @@ class WindowAggState:
                 "increase out_cap"
             )
             raise RuntimeError(msg)
-        if int(self.error_flag.item()) != 0:
-            msg = "keyed window state table overflowed; increase slots_pow"
-            raise RuntimeError(msg)
+        _check_error_flag(
+            int(self.error_flag.item()), "keyed window state table"
+        )
         if n == 0:
             return None
         return RecordBatch(
@@ -862,9 +1191,9 @@ class WindowAggState:
             return out
         self._close_ev.synchronize()
         n = int(self._outn_pin[0].item())
-        if int(self._outn_pin[1].item()) != 0:
-            msg = "keyed window state table overflowed; increase slots_pow"
-            raise RuntimeError(msg)
+        _check_error_flag(
+            int(self._outn_pin[1].item()), "keyed window state table"
+        )
         if n > self.out_cap:
             msg = (
                 f"window close produced {n} rows > out_cap "
@@ -957,6 +1286,7 @@ class WindowAggState:
 
         Returns (closed_rows, step_launch_ns: torch int64 tensor).
         """
+        self._ordered_only("native_run")
         import torch
 
         if self.cpu:
@@ -1039,6 +1369,7 @@ class WindowAggState:
         pool cycle of {insert, timestamp-bump} kernels is captured once
         and each replay costs a single hipGraphLaunch (latency mode;
         COUNT, single-pass).  Returns closed rows."""
+        self._ordered_only("native_run_graph")
         import torch
 
         if self.cpu or self.radix or self.dedup or self.mode != AGG_COUNT:
@@ -1108,13 +1439,17 @@ class WindowAggState:
             # sliding expansion during restore).
             ts = (wins * self.len_ms + self.align_ms).to(self.device)
             vals = torch.as_tensor(snap["vals"]).to(self.device)
+            # The synthetic timestamps are no event times (for sliding
+            # windows they run len/off times ahead of them): they must
+            # not reach the watermark scalar, which the late-tracking
+            # insert reads back when a batch has no `max_ts`.
             self.k.window_agg_insert(
                 keys,
                 ts,
                 vals,
                 self.tkeys,
                 self.tvals,
-                self.max_ts_dev,
+                torch.zeros_like(self.max_ts_dev),
                 self.error_flag,
                 self.align_ms,
                 self.len_ms,
@@ -1124,6 +1459,7 @@ class WindowAggState:
                 self.region_bits,
                 self.len_ms,
             )
+        self.max_ts_dev.clamp_(min=int(snap["max_ts"]))
         self.max_ts_host = snap["max_ts"]
         self.closed_horizon = snap["closed_horizon"]
 
@@ -1147,13 +1483,16 @@ class WindowAggState:
                 kw = (int(k), int(w))
                 self._table[kw] = self._table.get(kw, 0) + int(v)
             return
+        import torch
+
         self.k.window_agg_insert(
             batch.keys,
             batch.ts,
             batch.vals,
             self.tkeys,
             self.tvals,
-            self.max_ts_dev,
+            # Window labels, not event times: kept off the watermark.
+            torch.zeros_like(self.max_ts_dev),
             self.error_flag,
             self.align_ms,
             self.len_ms,

@@ -545,6 +545,16 @@ def keyed_window_agg(
     slowly when most keys hash into few table regions.
     :arg exchange: Force the RCCL exchange on/off; default: on iff
         torch.distributed is initialized with world > 1.
+
+    Ingestion must be watermark-ordered across batches (each batch's
+    events at or after the watermark set by the earlier ones, minus
+    `wait`): this operator uses the pipelined, lazy and exchange insert
+    paths, which do not track late events, and nothing checks the
+    ordering — an event behind the watermark is folded into a window
+    that may already have been emitted.  Disordered streams go through
+    `fold_window` / `count_window` over RecordBatches
+    (:mod:`bytewax_amd.operators.windowing`), which reports late
+    events; late tracking here is a later change.
     """
     import threading
 
@@ -760,6 +770,16 @@ def keyed_window_agg_str(
     Snapshots restore at the SAME world size (ownership is
     ``hash % world``; resuming at a different world would strand
     state at its old owner — rescale through the host path).
+
+    Ingestion must be watermark-ordered across batches (each batch's
+    events at or after the watermark set by the earlier ones, minus
+    `wait`): this operator uses the pipelined, lazy and exchange insert
+    paths, which do not track late events, and nothing checks the
+    ordering — an event behind the watermark is folded into a window
+    that may already have been emitted.  Disordered streams go through
+    `fold_window` / `count_window` over RecordBatches
+    (:mod:`bytewax_amd.operators.windowing`), which reports late
+    events; late tracking here is a later change.
     """
     import torch
 
@@ -940,6 +960,16 @@ def keyed_stats_agg(
     Use a very long `length` for an unwindowed whole-stream
     aggregation.  Emits dicts of columnar device tensors
     {keys, wins, cnt, sum, min, max} at window close / EOF.
+
+    Ingestion must be watermark-ordered across batches (each batch's
+    events at or after the watermark set by the earlier ones, minus
+    `wait`): this operator uses the pipelined, lazy and exchange insert
+    paths, which do not track late events, and nothing checks the
+    ordering — an event behind the watermark is folded into a window
+    that may already have been emitted.  Disordered streams go through
+    `fold_window` / `count_window` over RecordBatches
+    (:mod:`bytewax_amd.operators.windowing`), which reports late
+    events; late tracking here is a later change.
     """
     import threading
 

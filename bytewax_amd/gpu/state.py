@@ -15,6 +15,7 @@ twins for GPU-less test runs.
 from typing import Any, Dict, List, Optional, Tuple
 
 from . import AGG_COUNT, AGG_SUM, RecordBatch, _ms  # noqa: F401
+from . import _check_error_flag, _LateTracker, _split_late_cpu
 from ._ext import ext
 
 _I64_MAX = (1 << 63) - 1
@@ -22,7 +23,14 @@ _I64_MIN = -(1 << 63)
 
 
 class StatsAggState:
-    """Keyed (windowed) running count/sum/min/max on device."""
+    """Keyed (windowed) running count/sum/min/max on device.
+
+    With ``track_late=True`` disordered batches are accepted and late
+    events reported, with the semantics (and the sync-free `max_ts`
+    hint) documented on `WindowAggState`: an event with absolute
+    ``ts < watermark_of_earlier_batches - wait_ms`` joins no cell and
+    comes out of :meth:`take_late` exactly once.
+    """
 
     def __init__(
         self,
@@ -33,9 +41,19 @@ class StatsAggState:
         out_cap: int = 1 << 20,
         radix: bool = True,
         region_bits: int = 10,
+        track_late: bool = False,
+        wait_ms: int = 0,
+        late_cap: int = 0,
     ):
         import torch
 
+        self.track_late = track_late
+        self.wait_ms = wait_ms
+        self._late = (
+            _LateTracker(device, wait_ms, True, late_cap)
+            if track_late
+            else None
+        )
         self.device = device
         self.align_ms = align_ms
         self.len_ms = len_ms
@@ -111,6 +129,13 @@ class StatsAggState:
                 max_ts=batch.max_ts,
                 ts_base=batch.ts_base,
             )
+        late_args = ()
+        if self.track_late and not self.cpu:
+            lt = self._late
+            lt.reserve(len(batch), self.error_flag)
+            late_args = (
+                self.max_ts_host - self.wait_ms, lt.keys, lt.ts, lt.vals, lt.n
+            )
         if self.cpu:
             self._insert_cpu(batch)
         elif self.radix:
@@ -134,7 +159,12 @@ class StatsAggState:
                 self.rx_ov_vals = torch.empty(
                     ov, dtype=torch.int64, device=self.device
                 )
-            self.k.radix_stats_insert(
+            fn = (
+                self.k.radix_stats_insert_late
+                if late_args
+                else self.k.radix_stats_insert
+            )
+            fn(
                 batch.keys,
                 batch.ts,
                 batch.vals,
@@ -155,9 +185,11 @@ class StatsAggState:
                 self.len_ms,
                 batch.ts_base,
                 self.region_bits,
+                *late_args,
             )
         else:
-            self.k.stats_insert(
+            fn = self.k.stats_insert_late if late_args else self.k.stats_insert
+            fn(
                 batch.keys,
                 batch.ts,
                 batch.vals,
@@ -171,11 +203,40 @@ class StatsAggState:
                 self.align_ms,
                 self.len_ms,
                 batch.ts_base,
+                *late_args,
             )
-        if batch.max_ts is not None and batch.max_ts > self.max_ts_host:
-            self.max_ts_host = batch.max_ts
+        if late_args:
+            self._late.inserted()
+        if batch.max_ts is not None:
+            if batch.max_ts > self.max_ts_host:
+                self.max_ts_host = batch.max_ts
+        elif late_args:
+            # The next cutoff needs this batch's maximum: without the
+            # hint it has to come back from the device.
+            dev_max = int(self.max_ts_dev.item())
+            if dev_max > self.max_ts_host:
+                self.max_ts_host = dev_max
+
+    def take_late(self) -> Optional[RecordBatch]:
+        """Drain the late events accumulated since the last call
+        (`track_late` only): `keys`, absolute int64 `ts` (``ts_base``
+        0) and `vals`, one row per late event.  Synchronises with the
+        device."""
+        if self._late is None:
+            return None
+        return self._late.take(None if self.cpu else self.error_flag)
+
+    def late_drained(self) -> bool:
+        """True when :meth:`insert` had to drain late rows into the
+        host-side carry (see `WindowAggState.late_drained`)."""
+        return self._late is not None and bool(self._late.carry)
 
     def _insert_cpu(self, batch: RecordBatch) -> None:
+        if self.track_late:
+            # The rule of the LATE kernels (see WindowAggState).
+            batch = _split_late_cpu(
+                batch, self.max_ts_host - self.wait_ms, self._late
+            )
         keys = batch.keys.tolist()
         import torch
 
@@ -256,9 +317,7 @@ class StatsAggState:
         if n > self.out_cap:
             msg = f"stats extract produced {n} rows > out_cap"
             raise RuntimeError(msg)
-        if int(self.error_flag.item()) != 0:
-            msg = "stats table overflowed; increase slots_pow"
-            raise RuntimeError(msg)
+        _check_error_flag(int(self.error_flag.item()), "stats table")
         return {
             "keys": self.out_keys[:n].clone(),
             "wins": self.out_wins[:n].clone(),
@@ -333,14 +392,17 @@ class StatsAggState:
         #   cnt/sum arithmetically with a second pass.
         mn = torch.as_tensor(snap["min"]).to(self.device)
         mx = torch.as_tensor(snap["max"]).to(self.device)
+        # Window starts, not event times: kept off the watermark
+        # scalar (the late-tracking insert reads it back).
+        no_wm = torch.zeros_like(self.max_ts_dev)
         self.k.stats_insert(
             keys, ts, mn, self.tkeys, self.tcnt, self.tsum, self.tmin,
-            self.tmax, self.max_ts_dev, self.error_flag,
+            self.tmax, no_wm, self.error_flag,
             self.align_ms, self.len_ms, 0,
         )
         self.k.stats_insert(
             keys, ts, mx, self.tkeys, self.tcnt, self.tsum, self.tmin,
-            self.tmax, self.max_ts_dev, self.error_flag,
+            self.tmax, no_wm, self.error_flag,
             self.align_ms, self.len_ms, 0,
         )
         # Correct cnt/sum: current slots have cnt=2, sum=min+max; the

@@ -961,15 +961,46 @@ class _ColumnarWindowLogic(StatefulBatchLogic):
     Values are RecordBatches; emissions are
     `(COLUMNAR_WINDOW_ID, "E", closed_rows_RecordBatch)` — the same
     tagged-tuple protocol `_WindowLogic` uses, so the `window`
-    operator's unwrappers split the streams identically.  Ingestion
-    must be watermark-ordered (in-order columnar sources); the late
-    stream is not populated on this path.
+    operator's unwrappers split the streams identically.
+
+    Batches may arrive disordered.  The watermark is batch-granular:
+    the max, over all EARLIER batches, of the event timestamps and the
+    `max_ts` hints, minus the clock's wait; order inside a batch
+    carries no meaning.  An event below it is late: it joins no window
+    and is emitted once, no later than EOF, as part of a
+    `(COLUMNAR_WINDOW_ID, "L", RecordBatch(keys, absolute ts[, vals]))`
+    emission that reaches `WindowOut.late`.  One late row is one
+    EVENT on this path — not one row per overlapped window as the
+    host's sliding windower reports.  The decision is fused into the
+    insert kernels; late rows are read back only where the host
+    synchronises anyway (a window close, EOF, a snapshot, or the
+    state's late buffer filling up), so an ordered stream whose
+    batches carry `max_ts` pays no synchronisation between closes.
+    Rows drained by `snapshot()` (which cannot emit) are persisted in
+    the snapshot under ``"__late__"`` and emitted on the next
+    activation, or after a resume.
     """
 
     def __init__(self, spec: _ColumnarSpec, resume):
         self.spec = spec
         self.state = None  # built on first batch (device known then)
         self._resume = resume
+        #: Late RecordBatches drained but not yet emitted.
+        self._late_carry: List = []
+        if isinstance(resume, dict) and resume.get("__late__") is not None:
+            from ..gpu import RecordBatch
+            import torch
+
+            saved = resume["__late__"]
+            self._late_carry.append(
+                RecordBatch(
+                    torch.as_tensor(saved["keys"]),
+                    torch.as_tensor(saved["ts"]),
+                    torch.as_tensor(saved["vals"])
+                    if saved["vals"] is not None
+                    else None,
+                )
+            )
 
     def _ensure(self, batch) -> None:
         if self.state is not None:
@@ -987,6 +1018,8 @@ class _ColumnarWindowLogic(StatefulBatchLogic):
                 self.spec.len_ms,
                 slots_pow=22 if on_gpu else 16,
                 out_cap=1 << (22 if on_gpu else 16),
+                track_late=True,
+                wait_ms=self.spec.wait_ms,
             )
             if self._resume is not None:
                 self.state.restore_from_host(self._resume)
@@ -1001,10 +1034,22 @@ class _ColumnarWindowLogic(StatefulBatchLogic):
             out_cap=1 << (22 if on_gpu else 16),
             radix=on_gpu,
             off_ms=self.spec.off_ms,
+            track_late=True,
+            wait_ms=self.spec.wait_ms,
         )
         if self._resume is not None:
             self.state.restore_from_host(self._resume)
             self._resume = None
+
+    def _drain_late(self) -> None:
+        """Move the state's late rows into the carry (synchronises)."""
+        late = self.state.take_late()
+        if late is not None:
+            self._late_carry.append(late)
+
+    def _late_events(self) -> List:
+        carry, self._late_carry = self._late_carry, []
+        return [(COLUMNAR_WINDOW_ID, "L", late) for late in carry]
 
     def _stats_close(self, horizon) -> Optional[Any]:
         """Extract closed (key, window) stats rows as a RecordBatch of
@@ -1034,6 +1079,9 @@ class _ColumnarWindowLogic(StatefulBatchLogic):
         for batch in values:
             self._ensure(batch)
             self.state.insert(batch)
+        if self.state is None:
+            return (self._late_events(), False)
+        was_closed = self.state.closed_horizon
         if self.spec.mode in ("min", "max", "mean"):
             wm = self.state.max_ts_host
             horizon = (
@@ -1044,29 +1092,64 @@ class _ColumnarWindowLogic(StatefulBatchLogic):
             closed = self.state.close_due(self.spec.wait_ms)
         if closed is not None:
             events.append((COLUMNAR_WINDOW_ID, "E", closed))
+        # Late rows come back where the host synchronised anyway: a
+        # close that ran, or a drain the state's buffer bound forced.
+        if (
+            self.state.closed_horizon != was_closed
+            or self.state.late_drained()
+        ):
+            self._drain_late()
+        events.extend(self._late_events())
         return (events, False)
 
     def on_notify(self) -> Tuple[Iterable, bool]:
-        return ([], False)
+        return (self._late_events(), False)
 
     def on_eof(self) -> Tuple[Iterable, bool]:
         if self.state is None:
-            return ([], True)
+            return (self._late_events(), True)
         if self.spec.mode in ("min", "max", "mean"):
             final = self._stats_close(None)
         else:
             final = self.state.close_all()
-        if final is None:
-            return ([], True)
-        return ([(COLUMNAR_WINDOW_ID, "E", final)], True)
+        self._drain_late()
+        events = self._late_events()
+        if final is not None:
+            events.insert(0, (COLUMNAR_WINDOW_ID, "E", final))
+        return (events, True)
 
     def notify_at(self) -> Optional[datetime]:
         return None
 
+    def _late_snapshot(self):
+        """Carried late rows as host arrays (None when there are none)."""
+        import torch
+
+        if not self._late_carry:
+            return None
+        carry = self._late_carry
+        vals = None
+        if carry[0].vals is not None:
+            vals = torch.cat([b.vals.cpu() for b in carry]).numpy().copy()
+        return {
+            "keys": torch.cat([b.keys.cpu() for b in carry]).numpy().copy(),
+            "ts": torch.cat([b.ts.cpu() for b in carry]).numpy().copy(),
+            "vals": vals,
+        }
+
     def snapshot(self):
+        # Cannot emit: rows drained here are carried and persisted, and
+        # go out on the next activation (or after a resume).
         if self.state is None:
-            return {"__columnar__": self._resume}
-        return {"__columnar__": self.state.snapshot_to_host()}
+            snap = dict(self._resume) if self._resume is not None else None
+        else:
+            self._drain_late()
+            snap = self.state.snapshot_to_host()
+        if snap is not None:
+            # Without a state or resume data no batch was ever seen,
+            # so nothing can be carried.
+            snap["__late__"] = self._late_snapshot()
+        return {"__columnar__": snap}
 
 
 @dataclass
