@@ -69,11 +69,14 @@ static ScatterKind scatter_kind_env() {
   return SCAT_STAGED;
 }
 
-// Experimental coalesced-placement staged variant ("staged2"): only
-// consulted where it is implemented (COUNT, tumbling).
+// Write-combined staged variant ("staged2"): only consulted where it
+// is implemented (COUNT, tumbling, no late tracking).  An explicit
+// BYTEWAX_SCATTER=staged selects the plain staged kernel.
+#define SCATTER_STAGED2_DEFAULT true
 static bool scatter_staged2_env() {
   const char* s = std::getenv("BYTEWAX_SCATTER");
-  return s != nullptr && std::strncmp(s, "staged2", 7) == 0;
+  if (s == nullptr) return SCATTER_STAGED2_DEFAULT;
+  return std::strncmp(s, "staged2", 7) == 0;
 }
 
 // LDS-deduped region join (BYTEWAX_JOIN_LDS=0 falls back to the
@@ -1094,17 +1097,49 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged(
 }
 
 
-// Coalesced-placement variant of the staged scatter (COUNT,
-// tumbling): stage the tile's granted entries in LDS together with
-// their precomputed global positions, then write them back with a
-// LINEAR copy loop — consecutive lanes hit consecutive addresses
-// inside each segment's granule run, so the hardware coalesces ~8
-// scattered-by-segment events into one full-line transaction instead
-// of 8.  Probes the hypothesis that the scatter is bound by L2
-// random-store transaction rate (~1 tx/event in the default staged
-// kernel), not bytes.  Selected via BYTEWAX_SCATTER=staged2.
-template <typename TS = int64_t, int U = 16>
-__global__ __launch_bounds__(256) void k_radix_scatter_staged2(
+// Write-combined variant of the staged scatter (COUNT, tumbling, no
+// late tracking).  Same contract as k_radix_scatter_staged — the
+// `ev_packed` layout, SC_GRAN reservation of the shared cursors, the
+// sentinel-padded final flush, the capacity split to the overflow
+// spill and `max_ts` — so k_radix_agg cannot tell them apart.  What
+// changes is how a granted entry reaches memory: instead of one 8-byte
+// store per event from whichever lane happens to hold it (a wave store
+// touching 64 different lines), the tile's granted entries are staged
+// in LDS grouped by segment, and copied out in 16-byte pieces with
+// four adjacent lanes covering one 64-byte line.  A wave store then
+// writes 16 whole lines: 8x fewer store requests and 2x fewer store
+// instructions for the same bytes.
+//
+// Per tile (BLK * U events, four barriers):
+//   P1   classify (the columns were loaded a tile ahead), returning
+//        LDS atomic on the segment histogram: the old value is the
+//        event's rank in its segment for this tile, so no second
+//        cursor atomic is needed.  Then load the next tile's columns.
+//   P2a  thread b: tot = residual + hist, grant = tot & ~7, reserve
+//        `grant` on the shared cursor; wave scan of the grants.
+//   P2b  cross-wave step of the scan -> staging offset of segment b;
+//        one destination per granule into gdst[] (or GD_SPILL when the
+//        granule lies at or beyond `cap`: cap, bases and grants are
+//        multiples of 8, so a granule is wholly inside or outside);
+//        old residual drains to the head of the run.
+//   P3   events go to stage[off + rc + rank] when inside the grant,
+//        else to the residual array.
+//   P4   copy-out, lane p takes piece p.
+// The default for tumbling COUNT; BYTEWAX_SCATTER=staged2 names it,
+// BYTEWAX_SCATTER=staged selects the plain kernel instead.
+#define GD_SPILL 0xFFFFFFFFu
+
+// Dynamic LDS of k_radix_scatter_staged2 for a tile of `tile` events.
+static inline size_t staged2_lds_bytes(int64_t nseg, int64_t tile) {
+  size_t stage_n = (size_t)(tile + 7 * nseg);  // multiple of 8
+  return stage_n * 8                           // stage
+         + (size_t)nseg * SC_GRAN * 8          // res
+         + 3 * (size_t)nseg * sizeof(int)      // res_cnt, lhist, lpack
+         + (stage_n / SC_GRAN) * sizeof(uint32_t);  // gdst
+}
+
+template <typename TS = int64_t, int U = 16, int BLK = 512>
+__global__ __launch_bounds__(BLK) void k_radix_scatter_staged2(
     const int32_t* __restrict__ keys,
     const TS* __restrict__ ts,
     const int64_t* __restrict__ vals,  // unused (COUNT)
@@ -1127,24 +1162,27 @@ __global__ __launch_bounds__(256) void k_radix_scatter_staged2(
     int* __restrict__ error_flag,
     uint64_t win_m2,
     uint64_t win_maxfast) {
-  extern __shared__ char smem[];
-  const int nseg = (int)(((mask + 1) >> seg_bits));
-  const int T = (int)blockDim.x * U;
-  const int MAXSTAGE = T + 7 * 2048;  // upper bound; sized by host LDS
-  uint64_t* stage = (uint64_t*)smem;                       // [maxstage]
-  int* gpos = (int*)(smem + (size_t)(T + 7 * nseg) * 8);   // [maxstage]
-  uint64_t* res = (uint64_t*)(smem + (size_t)(T + 7 * nseg) * 12);
-  int* res_cnt = (int*)((char*)res + (size_t)nseg * SC_GRAN * 8);
-  int* lhist = res_cnt + nseg;
-  int* lbase = lhist + nseg;
-  int* ltoff = lbase + nseg;
-  int* lvirt = ltoff + nseg;
-  int* lgrant = lvirt + nseg;
-  int* ltotal = lgrant + nseg;  // [1]
-  (void)MAXSTAGE;
-  for (int b = threadIdx.x; b < nseg; b += blockDim.x) {
-    res_cnt[b] = 0;
-    lhist[b] = 0;
+  constexpr int T = BLK * U;
+  constexpr int NW = BLK / WAVE;
+  // lpack: staging offset (14 bits) | residual count (3) | grant (14+).
+  static_assert(T + 7 * BLK < (1 << 14), "staging offset must fit 14 bits");
+  static_assert(T <= (1 << 13), "tile rank shares a word with the segment");
+  extern __shared__ __attribute__((aligned(16))) char smem_wc[];
+  __shared__ int s_wtot[NW];
+  const int nseg = (int)(((mask + 1) >> seg_bits));  // host: nseg <= BLK
+  const int stage_n = T + 7 * nseg;
+  uint64_t* stage = (uint64_t*)smem_wc;        // [stage_n]
+  uint64_t* res = stage + stage_n;             // [nseg][SC_GRAN]
+  int* res_cnt = (int*)(res + (size_t)nseg * SC_GRAN);  // [nseg]
+  int* lhist = res_cnt + nseg;                 // [nseg]
+  int* lpack = lhist + nseg;                   // [nseg]
+  uint32_t* gdst = (uint32_t*)(lpack + nseg);  // [stage_n / SC_GRAN]
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wave = tid / WAVE;
+  if (tid < nseg) {
+    res_cnt[tid] = 0;
+    lhist[tid] = 0;
   }
   __syncthreads();
 
@@ -1154,127 +1192,127 @@ __global__ __launch_bounds__(256) void k_radix_scatter_staged2(
     else atomicOr(error_flag, 1);
   };
 
-  const int64_t tile = (int64_t)blockDim.x * U;
-  int64_t local_max = 0;
-  for (int64_t t0 = (int64_t)blockIdx.x * tile; t0 < n;
-       t0 += (int64_t)gridDim.x * tile) {
-    uint64_t pk[U];
-    int sg[U];
-    // P1: classify + histogram.
+  // Raw columns of one tile, loaded a tile ahead.  The loads carry no
+  // branch (the index is clamped, the lane is masked in P1): a branch
+  // around each load makes U dependent round trips out of one batch,
+  // and with one workgroup per CU nothing else would hide them.
+  int32_t rk[U];
+  TS rt[U];
+  auto load_tile = [&](int64_t t0) {
+#pragma unroll
     for (int u = 0; u < U; ++u) {
-      int64_t i = t0 + (int64_t)u * blockDim.x + threadIdx.x;
-      sg[u] = -1;
-      if (i >= n) continue;
-      int64_t t = (int64_t)ts[i] + ts_base;
-      if (t > local_max) local_max = t;
+      int64_t i = t0 + u * BLK + tid;
+      if (i > n - 1) i = n - 1;
+      rk[u] = keys[i];
+      rt[u] = ts[i];
+    }
+  };
+  const int64_t stride = (int64_t)gridDim.x * T;
+  int64_t local_max = 0;
+  int64_t t0 = (int64_t)blockIdx.x * T;
+  if (t0 < n) load_tile(t0);
+  for (; t0 < n; t0 += stride) {
+    uint64_t pk[U];
+    int sr[U];  // (rank << 13) | segment, or -1 past the end
+    // P1: classify, rank.
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      int64_t i = t0 + u * BLK + tid;
+      int64_t t = (int64_t)rt[u] + ts_base;
       int64_t win = win_of(t, align_ms, len_ms, win_m2, win_maxfast);
       uint64_t packed =
-          ((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)keys[i];
+          ((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)rk[u];
       pk[u] = packed;
       int b = (int)region_of(mix64(packed), mask, seg_bits);
-      sg[u] = b;
-      atomicAdd(&lhist[b], 1);
-    }
-    __syncthreads();
-    // P2: granule grants + in-tile staging offsets (exclusive scan of
-    // the per-segment grants).
-    for (int b = threadIdx.x; b < nseg; b += blockDim.x) {
-      int tot = res_cnt[b] + lhist[b];
-      int grant = tot & ~(SC_GRAN - 1);
-      lgrant[b] = grant;
-      lbase[b] = grant > 0 ? atomicAdd(&gcursors[b], grant) : 0;
-      // Virtual positions count residual + new; ungranted segments
-      // keep their residual in place and append after it.
-      lvirt[b] = res_cnt[b];
-      ltoff[b] = grant;  // scanned in place below
-    }
-    __syncthreads();
-    // Hillis-Steele inclusive scan over ltoff[nseg], then shift to
-    // exclusive via (incl - grant).
-    for (int d = 1; d < nseg; d <<= 1) {
-      int v[8];
-      int nb = 0;
-      for (int b = threadIdx.x; b < nseg; b += blockDim.x) {
-        v[nb++] = b >= d ? ltoff[b - d] : 0;
+      sr[u] = -1;
+      if (i < n) {
+        if (t > local_max) local_max = t;
+        sr[u] = (atomicAdd(&lhist[b], 1) << 13) | b;
       }
-      __syncthreads();
-      nb = 0;
-      for (int b = threadIdx.x; b < nseg; b += blockDim.x) {
-        ltoff[b] += v[nb++];
-      }
-      __syncthreads();
     }
-    if (threadIdx.x == 0) ltotal[0] = ltoff[nseg - 1];
+    if (t0 + stride < n) load_tile(t0 + stride);
     __syncthreads();
-    // P3a: drain old residual into staging (virtual slots 0..rc).
-    for (int b = threadIdx.x; b < nseg; b += blockDim.x) {
-      int grant = lgrant[b];
+    // P2a: grants, cursor reservation, wave scan of the grants.
+    int rc = 0, grant = 0, gb = 0;
+    if (tid < nseg) {
+      rc = res_cnt[tid];
+      int tot = rc + lhist[tid];
+      grant = tot & ~(SC_GRAN - 1);
+      if (grant > 0) gb = atomicAdd(&gcursors[tid], grant);
+      res_cnt[tid] = tot - grant;
+      lhist[tid] = 0;
+    }
+    int incl = grant;
+    for (int o = 1; o < WAVE; o <<= 1) {
+      int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    if (lane == WAVE - 1) s_wtot[wave] = incl;
+    __syncthreads();
+    // P2b: staging offsets, granule destinations, residual drain.
+    int total = 0, woff = 0;
+    for (int w = 0; w < NW; ++w) {
+      int v = s_wtot[w];
+      if (w < wave) woff += v;
+      total += v;
+    }
+    if (tid < nseg) {
+      int off = woff + incl - grant;
+      lpack[tid] = off | (rc << 14) | (grant << 17);
       if (grant > 0) {
-        int rc = res_cnt[b];
-        int off = ltoff[b] - grant;
-        int gb = lbase[b];
-        for (int j = 0; j < rc; ++j) {
+        // All seven residual slots, whatever rc is: the run holds at
+        // least a granule, and P3 (behind the barrier) fills every
+        // slot from rc up to the grant with an event of this tile.
+#pragma unroll
+        for (int j = 0; j < SC_GRAN - 1; ++j)
+          stage[off + j] = res[(size_t)tid * SC_GRAN + j];
+        for (int j = 0; j < grant; j += SC_GRAN) {
           int64_t gp = (int64_t)gb + j;
-          if (gp < cap) {
-            stage[off + j] = res[(size_t)b * SC_GRAN + j];
-            gpos[off + j] = (int)((int64_t)b * cap + gp);
-          } else {
-            stage[off + j] = 0;
-            gpos[off + j] = -1;
-            spill(res[(size_t)b * SC_GRAN + j]);
-          }
+          gdst[(off + j) / SC_GRAN] =
+              gp < cap ? (uint32_t)(((int64_t)tid * cap + gp) / SC_GRAN)
+                       : GD_SPILL;
         }
       }
     }
     __syncthreads();
-    // P3b: place new events (staged if granted, else residual).
+    // P3: place this tile's events (staged if granted, else residual).
     for (int u = 0; u < U; ++u) {
-      int b = sg[u];
-      if (b < 0) continue;
-      int virt = atomicAdd(&lvirt[b], 1);
-      int grant = lgrant[b];
-      if (virt < grant) {
-        int off = ltoff[b] - grant + virt;
-        int64_t gp = (int64_t)lbase[b] + virt;
-        if (gp < cap) {
-          stage[off] = pk[u];
-          gpos[off] = (int)((int64_t)b * cap + gp);
-        } else {
-          stage[off] = 0;
-          gpos[off] = -1;
-          spill(pk[u]);
-        }
+      if (sr[u] < 0) continue;
+      int b = sr[u] & ((1 << 13) - 1);
+      int w = lpack[b];
+      int vpos = ((w >> 14) & 7) + (sr[u] >> 13);
+      int g = w >> 17;
+      if (vpos < g) stage[(w & ((1 << 14) - 1)) + vpos] = pk[u];
+      else res[(size_t)b * SC_GRAN + (vpos - g)] = pk[u];
+    }
+    __syncthreads();
+    // P4: copy-out.  Piece p is entries 2p, 2p+1; four adjacent lanes
+    // cover one 64 B line of ev_packed.  The next tile's P1 touches
+    // only lhist, and its P2b (the next writer of stage/gdst) lies
+    // behind two barriers, so no barrier closes the tile.
+    for (int p = tid; p < total / 2; p += BLK) {
+      ulonglong2 v = *(const ulonglong2*)(stage + 2 * p);
+      uint32_t d = gdst[p / 4];
+      if (d != GD_SPILL) {
+        *(ulonglong2*)(ev_packed + (int64_t)d * SC_GRAN + 2 * (p & 3)) = v;
       } else {
-        res[(size_t)b * SC_GRAN + (virt - grant)] = pk[u];
+        if (v.x != EMPTY_SLOT) spill(v.x);
+        if (v.y != EMPTY_SLOT) spill(v.y);
       }
     }
-    __syncthreads();
-    // P4: coalesced copy-out — consecutive threads write consecutive
-    // staged slots; slots are segment-grouped and granule-aligned, so
-    // adjacent lanes hit adjacent addresses of the same 64 B lines.
-    int total = ltotal[0];
-    for (int j = threadIdx.x; j < total; j += blockDim.x) {
-      int gp = gpos[j];
-      if (gp >= 0) ev_packed[gp] = stage[j];
-    }
-    // P5: carry leftovers.
-    for (int b = threadIdx.x; b < nseg; b += blockDim.x) {
-      res_cnt[b] = lvirt[b] - lgrant[b];
-      if (res_cnt[b] < 0) res_cnt[b] = 0;
-      lhist[b] = 0;
-    }
-    __syncthreads();
   }
+  __syncthreads();
   // Final flush: sentinel-padded granules, like the default staged.
-  for (int b = threadIdx.x; b < nseg; b += blockDim.x) {
-    int rc = res_cnt[b];
-    if (rc == 0) continue;
-    int gb = atomicAdd(&gcursors[b], SC_GRAN);
-    for (int j = 0; j < SC_GRAN; ++j) {
-      uint64_t p = j < rc ? res[(size_t)b * SC_GRAN + j] : EMPTY_SLOT;
-      int64_t gp = (int64_t)gb + j;
-      if (gp < cap) ev_packed[(int64_t)b * cap + gp] = p;
-      else if (p != EMPTY_SLOT) spill(p);
+  if (tid < nseg) {
+    int rc = res_cnt[tid];
+    if (rc > 0) {
+      int gb = atomicAdd(&gcursors[tid], SC_GRAN);
+      for (int j = 0; j < SC_GRAN; ++j) {
+        uint64_t p = j < rc ? res[(size_t)tid * SC_GRAN + j] : EMPTY_SLOT;
+        int64_t gp = (int64_t)gb + j;
+        if (gp < cap) ev_packed[(int64_t)tid * cap + gp] = p;
+        else if (p != EMPTY_SLOT) spill(p);
+      }
     }
   }
   for (int off = WAVE / 2; off > 0; off >>= 1) {
@@ -1641,7 +1679,31 @@ __global__ void k_close_extract(
 // caller swaps tables afterwards and resets the old one
 // asynchronously.  Migrated cells are unique by construction so the
 // rebuild cannot create duplicate chains.
-__global__ void k_close_migrate(
+//
+// Output rows are reserved once per CM_CHUNK-slot chunk: a block loads
+// the chunk's keys 16 bytes per lane into registers, ranks its takes
+// with a wave scan plus a cross-wave LDS step, and thread 0 does the
+// one `atomicAdd(out_n, chunk_total)`.  A 2^22-slot table makes 2048
+// same-address atomics per close where the per-wave reservation made
+// one per wave with a due cell.  Rows past `cap` are counted, not
+// written.
+//
+// Migration stores the value plainly after `find_slot_r` has claimed
+// the slot.  That is exact because (1) the target table is fresh
+// (keys EMPTY, values zero) and each migrated cell is unique, so
+// exactly one thread of this kernel claims a given slot and nobody
+// else touches its value; and (2) nothing else writes the target
+// while the kernel runs: every writer of either table (the insert and
+// aggregation kernels, the overflow drain, the resets of the retired
+// table) is enqueued on the same stream as the close, before or after
+// it.  The side stream of the two-stream insert runs only the
+// scatter, which writes the event buffers and never a table.
+#define CM_BLK 256
+#define CM_PER 8  // slots per thread per chunk (four 16-byte loads)
+#define CM_CHUNK (CM_BLK * CM_PER)
+#define CM_MAX_GRID 1024  // four blocks per CU
+
+__global__ __launch_bounds__(CM_BLK) void k_close_migrate(
     const uint64_t* __restrict__ tkeys,
     const unsigned long long* __restrict__ tvals,
     int64_t nslots,
@@ -1656,38 +1718,76 @@ __global__ void k_close_migrate(
     int* __restrict__ out_n,
     int64_t cap,
     int* __restrict__ error_flag) {
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; i < nslots; i += stride) {
-    uint64_t k = tkeys[i];
-    bool occupied = (k != EMPTY_SLOT);
-    int32_t win = 0;
-    bool take = false;
-    if (occupied) {
-      win = (int32_t)(uint32_t)(k >> 32);
-      take = (int64_t)win < win_hi;
-      if (!take) {
-        if (!hash_add(nkeys, nvals, mask, region_bits, k, tvals[i])) {
-          atomicOr(error_flag, 1);
+  constexpr int NW = CM_BLK / WAVE;
+  // Double-buffered by chunk parity: two barriers per chunk suffice.
+  __shared__ int s_wave[2][NW];
+  __shared__ int s_base[2];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const bool vec = ((((uintptr_t)tkeys) | ((uintptr_t)tvals)) & 15) == 0;
+  const int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  int par = 0;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x, par ^= 1) {
+    const int64_t c0 = c * CM_CHUNK;
+    uint64_t k[CM_PER];
+    unsigned long long v[CM_PER];
+    for (int j = 0; j < CM_PER / 2; ++j) {
+      int64_t s = c0 + (int64_t)j * (CM_BLK * 2) + threadIdx.x * 2;
+      if (vec && s + 1 < nslots) {
+        ulonglong2 kk = *(const ulonglong2*)(tkeys + s);
+        k[2 * j] = kk.x;
+        k[2 * j + 1] = kk.y;
+        v[2 * j] = 0;
+        v[2 * j + 1] = 0;
+        if (kk.x != EMPTY_SLOT || kk.y != EMPTY_SLOT) {
+          ulonglong2 vv = *(const ulonglong2*)(tvals + s);
+          v[2 * j] = vv.x;
+          v[2 * j + 1] = vv.y;
+        }
+      } else {
+        for (int q = 0; q < 2; ++q) {
+          k[2 * j + q] = s + q < nslots ? tkeys[s + q] : EMPTY_SLOT;
+          v[2 * j + q] = k[2 * j + q] != EMPTY_SLOT ? tvals[s + q] : 0;
         }
       }
     }
-    unsigned long long ball = __ballot(take);
-    int lane = threadIdx.x & (WAVE - 1);
-    if (ball != 0) {
-      int wave_total = __popcll(ball);
-      int rank = __popcll(ball & ((1ULL << lane) - 1ULL));
-      int base = 0;
-      int lead = __ffsll((unsigned long long)ball) - 1;
-      if (lane == lead) base = atomicAdd(out_n, wave_total);
-      base = __shfl(base, lead);
-      if (take) {
-        int64_t idx = base + rank;
+    unsigned takem = 0;
+    for (int q = 0; q < CM_PER; ++q) {
+      if (k[q] == EMPTY_SLOT) continue;
+      int32_t win = (int32_t)(uint32_t)(k[q] >> 32);
+      if ((int64_t)win < win_hi) {
+        takem |= 1u << q;
+      } else {
+        uint64_t slot = find_slot_r(nkeys, mask, region_bits, k[q]);
+        if (slot == ~0ULL) atomicOr(error_flag, 1);
+        else nvals[slot] = v[q];
+      }
+    }
+    const int cnt = __popc(takem);
+    int incl = cnt;
+    for (int off = 1; off < WAVE; off <<= 1) {
+      int o = __shfl_up(incl, off);
+      if (lane >= off) incl += o;
+    }
+    if (lane == WAVE - 1) s_wave[par][wave] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int total = 0;
+      for (int w = 0; w < NW; ++w) total += s_wave[par][w];
+      s_base[par] = total > 0 ? atomicAdd(out_n, total) : 0;
+    }
+    __syncthreads();
+    if (takem != 0) {
+      int64_t idx = (int64_t)s_base[par] + (incl - cnt);
+      for (int w = 0; w < wave; ++w) idx += s_wave[par][w];
+      for (int q = 0; q < CM_PER; ++q) {
+        if (!((takem >> q) & 1u)) continue;
         if (idx < cap) {
-          out_keys[idx] = (int32_t)(uint32_t)(k & 0xFFFFFFFFULL);
-          out_wins[idx] = win;
-          out_vals[idx] = (int64_t)tvals[i];
+          out_keys[idx] = (int32_t)(uint32_t)(k[q] & 0xFFFFFFFFULL);
+          out_wins[idx] = (int32_t)(uint32_t)(k[q] >> 32);
+          out_vals[idx] = (int64_t)v[q];
         }
+        ++idx;
       }
     }
   }
@@ -3101,6 +3201,118 @@ void window_agg_insert_late(
                          off_ms, &sink);
 }
 
+static unsigned device_cu_count() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
+                              dev) == hipSuccess &&
+        v > 0)
+      cus = v;
+    else
+      cus = 256;
+  }
+  return (unsigned)cus;
+}
+
+// The one place that picks and launches the staged COUNT scatter
+// without late tracking (tumbling or sliding; `xf` is the sliding
+// expansion factor).  radix_window_insert, radix_scatter_only and the
+// native step loop all come through here, so a variant is reachable,
+// and the default, everywhere or nowhere.
+//
+// Tumbling windows take the write-combined kernel (staged2) when it is
+// selected, its LDS fits a CU and `ev_packed` is 16-byte aligned;
+// everything else takes k_radix_scatter_staged.  Knobs (A/B only):
+// BYTEWAX_SCATTER_THREADS, BYTEWAX_SCATTER_U, BYTEWAX_SCATTER_BLOCKS.
+template <typename TSV>
+static void launch_count_staged(
+    hipStream_t stream, const int32_t* keys, const TSV* ts, int64_t n,
+    int64_t xf, int64_t align_ms, int64_t len_ms, int64_t off_ms,
+    int64_t ts_base, uint64_t mask, int seg_bits, int64_t nseg, int64_t cap,
+    int* gcur, uint64_t* evp, int* ovc, uint64_t* ovp, int64_t ov_cap,
+    unsigned long long* max_ts, int* err, uint64_t win_m2,
+    uint64_t win_maxfast, bool overlapped) {
+  int env_u = 0, env_threads = 0, env_blocks = 0;
+  if (const char* e = std::getenv("BYTEWAX_SCATTER_U")) env_u = atoi(e);
+  if (const char* e = std::getenv("BYTEWAX_SCATTER_THREADS"))
+    env_threads = atoi(e);
+  if (const char* e = std::getenv("BYTEWAX_SCATTER_BLOCKS")) {
+    int v = atoi(e);
+    if (v > 0) env_blocks = v;
+  }
+  auto go = [&](auto kern, int threads, int u, unsigned cap_gs, size_t lds,
+                auto... extra) {
+    int64_t tile = (int64_t)threads * u;
+    int64_t gs = (n * xf + tile - 1) / tile;
+    if (env_blocks > 0) cap_gs = (unsigned)env_blocks;
+    if (gs > (int64_t)cap_gs) gs = cap_gs;
+    if (gs < 1) gs = 1;
+    hipLaunchKernelGGL(
+        kern, dim3((unsigned)gs), dim3((unsigned)threads), lds, stream, keys,
+        ts, (const int64_t*)nullptr, n, align_ms, len_ms, off_ms, ts_base,
+        mask, seg_bits, cap, gcur, evp, (int64_t*)nullptr, ovc, ovp,
+        (int64_t*)nullptr, ov_cap, max_ts, err, win_m2, win_maxfast,
+        extra...);
+    // A refused launch (LDS budget, bad configuration) must not pass
+    // for an empty batch.
+    HIP_CHECK(hipGetLastError());
+  };
+  if (xf == 1 && scatter_staged2_env() && (((uintptr_t)evp) & 15) == 0) {
+    // 512 x 16: one workgroup per CU (LDS-bound), 8192-event tiles.
+    // 1024 x 8 keeps 16 waves per CU and measured 4 % faster alone
+    // (325 against 338 us), but its 128-VGPR budget spills 12 bytes
+    // per lane (36 with int64 timestamps) once the next tile's columns
+    // are held in registers; 512 x 16 has 256 and no scratch.
+    // One block per CU, each walking its share of the tiles: measured
+    // fastest when the scatter has the chip to itself (1024 x 8: 325
+    // us at 256 blocks, 351 at 512, 407 at 1024 for the 64M-event
+    // batch), and the padded final flush shrinks with it.
+    // `overlapped`: the caller runs the aggregation of the previous
+    // batch on another stream meanwhile.  Its 128 KB workgroups cannot
+    // share a CU with this kernel's, so some blocks start late; two
+    // blocks per CU halve the share a late block drags behind it.
+    const unsigned cus = device_cu_count() * (overlapped ? 2u : 1u);
+    int threads = env_threads == 1024 ? 1024 : 512;
+    int u = threads == 512 && env_u != 8 ? 16 : 8;
+    size_t lds = staged2_lds_bytes(nseg, (int64_t)threads * u);
+    if (nseg <= threads && lds <= 160 * 1024) {
+      if (threads == 1024)
+        go((k_radix_scatter_staged2<TSV, 8, 1024>), 1024, 8, cus, lds);
+      else if (u == 16)
+        go((k_radix_scatter_staged2<TSV, 16, 512>), 512, 16, cus, lds);
+      else
+        go((k_radix_scatter_staged2<TSV, 8, 512>), 512, 8, cus, lds);
+      return;
+    }
+  }
+  // One tile = blockDim * U events; enough blocks to fill the chip at
+  // the REGISTER-bounded occupancy (98 VGPRs: two 512-thread
+  // workgroups per CU, where the 40 KB staging LDS alone would allow
+  // four), few enough to keep the end-of-kernel residual padding
+  // small.  512-thread workgroups measured fastest (60.1 vs 56.6e9 at
+  // 256, 57.2 at 1024 — see profiles/).
+  size_t lds = (size_t)nseg * SC_GRAN * 8 + 4 * (size_t)nseg * sizeof(int);
+  int threads = 512;
+  if (env_threads == 256 || env_threads == 1024) threads = env_threads;
+  if (threads == 512)
+    go((k_radix_scatter_staged<AGG_COUNT, TSV, 16, 512>), 512, 16, 1024u,
+       lds, NO_LATE_ARGS);
+  else if (threads == 1024)
+    go((k_radix_scatter_staged<AGG_COUNT, TSV, 16, 1024>), 1024, 16, 1024u,
+       lds, NO_LATE_ARGS);
+  else if (env_u == 8)
+    go((k_radix_scatter_staged<AGG_COUNT, TSV, 8>), 256, 8, 1024u, lds,
+       NO_LATE_ARGS);
+  else if (env_u == 32)
+    go((k_radix_scatter_staged<AGG_COUNT, TSV, 32>), 256, 32, 1024u, lds,
+       NO_LATE_ARGS);
+  else
+    go((k_radix_scatter_staged<AGG_COUNT, TSV, 16>), 256, 16, 1024u, lds,
+       NO_LATE_ARGS);
+}
+
 static void radix_window_insert_impl(
     torch::Tensor keys,
     torch::Tensor ts,
@@ -3314,54 +3526,22 @@ static void radix_window_insert_impl(
     unsigned gx = (unsigned)n_blocks(sg.n, 256);
     if (env_blocks > 0 && (unsigned)env_blocks < gx) gx = (unsigned)env_blocks;
     if (kind == SCAT_STAGED) {
-      // One tile = blockDim * U events; enough blocks to fill the
-      // chip at the REGISTER-bounded occupancy (98 VGPRs: two
-      // 512-thread workgroups per CU, where the 40 KB staging LDS
-      // alone would allow four), few enough to keep the
-      // end-of-kernel residual padding small.  U (events per thread
-      // per tile) tunable via BYTEWAX_SCATTER_U (8/16/32).
-      int su = 16;
-      if (const char* e = std::getenv("BYTEWAX_SCATTER_U")) {
-        int v = atoi(e);
-        if (v == 8 || v == 16 || v == 32) su = v;
-      }
-      // 512-thread workgroups measured fastest for the COUNT staged
-      // scatter (60.1 vs 56.6e9 at 256, 57.2 at 1024 — see profiles/).
-      int sthreads = mode == AGG_COUNT ? 512 : 256;
-      if (const char* e = std::getenv("BYTEWAX_SCATTER_THREADS")) {
-        int v = atoi(e);
-        if (v == 256 || v == 512 || v == 1024) sthreads = v;
-      }
-      scat_threads = (unsigned)sthreads;
-      unsigned cap_gs = env_blocks > 0 ? (unsigned)env_blocks : 1024u;
-      unsigned gs =
-          (unsigned)((sg.n * xf + sthreads * su - 1) / (sthreads * su));
-      if (gs > cap_gs) gs = cap_gs;
-      if (gs < 1) gs = 1;
-      size_t s2_lds = (size_t)(256 * 16 + 7 * nseg) * 12 +
-                      (size_t)nseg * SC_GRAN * 8 +
-                      7 * (size_t)nseg * sizeof(int) + 16;
-      if (mode == AGG_COUNT && xf == 1 && scatter_staged2_env() &&
-          s2_lds <= 160 * 1024) {
-        scat_threads = 256;
-        scat(k_radix_scatter_staged2<TSV>, tsptr, sg, gs, s2_lds);
-      } else if (mode == AGG_COUNT) {
-        if (sthreads == 512)
-          scat((k_radix_scatter_staged<AGG_COUNT, TSV, 16, 512>), tsptr,
-               sg, gs, staged_lds, NO_LATE_ARGS);
-        else if (sthreads == 1024)
-          scat((k_radix_scatter_staged<AGG_COUNT, TSV, 16, 1024>), tsptr,
-               sg, gs, staged_lds, NO_LATE_ARGS);
-        else if (su == 8)
-          scat(k_radix_scatter_staged<AGG_COUNT, TSV, 8>, tsptr, sg, gs,
-               staged_lds, NO_LATE_ARGS);
-        else if (su == 32)
-          scat(k_radix_scatter_staged<AGG_COUNT, TSV, 32>, tsptr, sg, gs,
-               staged_lds, NO_LATE_ARGS);
-        else
-          scat(k_radix_scatter_staged<AGG_COUNT, TSV, 16>, tsptr, sg, gs,
-               staged_lds, NO_LATE_ARGS);
+      if (mode == AGG_COUNT) {
+        launch_count_staged<TSV>(
+            stream, keys.data_ptr<int32_t>() + sg.off, tsptr + sg.off, sg.n,
+            xf, align_ms, len_ms, off_ms, sg.base, mask, seg_bits, nseg, cap,
+            gcursors.data_ptr<int32_t>(),
+            (uint64_t*)ev_packed.data_ptr<int64_t>(),
+            ov_cursor.data_ptr<int32_t>(),
+            (uint64_t*)ov_packed.data_ptr<int64_t>(), ov_packed.numel(),
+            (unsigned long long*)max_ts.data_ptr<int64_t>(),
+            error_flag.data_ptr<int32_t>(), win_m2, win_maxfast,
+            /*overlapped=*/false);
       } else {
+        unsigned cap_gs = env_blocks > 0 ? (unsigned)env_blocks : 1024u;
+        unsigned gs = (unsigned)((sg.n * xf + 256 * 16 - 1) / (256 * 16));
+        if (gs > cap_gs) gs = cap_gs;
+        if (gs < 1) gs = 1;
         scat_threads = 256;
         scat(k_radix_scatter_staged<AGG_SUM, TSV>, tsptr, sg, gs,
              staged_lds, NO_LATE_ARGS);
@@ -3623,14 +3803,16 @@ void radix_scatter_only(
     using TSV = std::remove_const_t<std::remove_pointer_t<decltype(tsptr)>>;
     if (kind == SCAT_STAGED) {
       if (mode == AGG_COUNT) {
-        // 512-thread workgroups (see radix_window_insert).
-        unsigned gs = (unsigned)((sg.n + 8191) / 8192);
-        if (gs > 1024) gs = 1024;
-        if (gs < 1) gs = 1;
-        scat_threads = 512;
-        scat((k_radix_scatter_staged<AGG_COUNT, TSV, 16, 512>), tsptr,
-             sg, gs, staged_lds, NO_LATE_ARGS);
-        scat_threads = 256;
+        launch_count_staged<TSV>(
+            stream, keys.data_ptr<int32_t>() + sg.off, tsptr + sg.off, sg.n,
+            xf, align_ms, len_ms, off_ms, sg.base, mask, seg_bits, nseg, cap,
+            gcursors.data_ptr<int32_t>(),
+            (uint64_t*)ev_packed.data_ptr<int64_t>(),
+            ov_cursor.data_ptr<int32_t>(),
+            (uint64_t*)ov_packed.data_ptr<int64_t>(), ov_packed.numel(),
+            (unsigned long long*)max_ts.data_ptr<int64_t>(),
+            error_flag.data_ptr<int32_t>(), win_m2, win_maxfast,
+            /*overlapped=*/true);
       } else {
         unsigned gs = (unsigned)((sg.n + 4095) / 4096);
         if (gs > 1024) gs = 1024;
@@ -3787,6 +3969,30 @@ void radix_v2_window_insert(
       (int)region_bits, error_flag.data_ptr<int32_t>());
 }
 
+// One launch shape for every close that reclaims (see k_close_migrate).
+static void launch_close_migrate(
+    hipStream_t stream, const torch::Tensor& tkeys,
+    const torch::Tensor& tvals, int64_t win_hi, const torch::Tensor& nkeys,
+    const torch::Tensor& nvals, int64_t region_bits,
+    const torch::Tensor& out_keys, const torch::Tensor& out_wins,
+    const torch::Tensor& out_vals, const torch::Tensor& out_n,
+    const torch::Tensor& error_flag) {
+  int64_t nslots = tkeys.numel();
+  int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  if (nchunks < 1) nchunks = 1;
+  unsigned grid = (unsigned)(nchunks < CM_MAX_GRID ? nchunks : CM_MAX_GRID);
+  hipLaunchKernelGGL(
+      k_close_migrate, dim3(grid), dim3(CM_BLK), 0, stream,
+      (const uint64_t*)tkeys.data_ptr<int64_t>(),
+      (const unsigned long long*)tvals.data_ptr<int64_t>(), nslots, win_hi,
+      (uint64_t*)nkeys.data_ptr<int64_t>(),
+      (unsigned long long*)nvals.data_ptr<int64_t>(),
+      (uint64_t)(nslots - 1), (int)region_bits,
+      out_keys.data_ptr<int32_t>(), out_wins.data_ptr<int32_t>(),
+      out_vals.data_ptr<int64_t>(), out_n.data_ptr<int32_t>(),
+      out_keys.numel(), error_flag.data_ptr<int32_t>());
+}
+
 int64_t close_extract(
     torch::Tensor tkeys,
     torch::Tensor tvals,
@@ -3830,21 +4036,13 @@ void close_migrate(
     torch::Tensor error_flag) {
   check_dev(tkeys, torch::kInt64, "tkeys");
   check_dev(nkeys, torch::kInt64, "nkeys");
+  check_dev(tvals, torch::kInt64, "tvals");
+  check_dev(nvals, torch::kInt64, "nvals");
   int64_t nslots = tkeys.numel();
   TORCH_CHECK(nkeys.numel() == nslots, "table size mismatch");
-  auto stream = at::hip::getCurrentHIPStream();
-  dim3 block(256);
-  dim3 grid(n_blocks(nslots, 256));
-  hipLaunchKernelGGL(
-      k_close_migrate, grid, block, 0, stream,
-      (const uint64_t*)tkeys.data_ptr<int64_t>(),
-      (const unsigned long long*)tvals.data_ptr<int64_t>(), nslots, win_hi,
-      (uint64_t*)nkeys.data_ptr<int64_t>(),
-      (unsigned long long*)nvals.data_ptr<int64_t>(),
-      (uint64_t)(nslots - 1), (int)region_bits,
-      out_keys.data_ptr<int32_t>(), out_wins.data_ptr<int32_t>(),
-      out_vals.data_ptr<int64_t>(), out_n.data_ptr<int32_t>(),
-      out_keys.numel(), error_flag.data_ptr<int32_t>());
+  launch_close_migrate(
+      at::hip::getCurrentHIPStream(), tkeys, tvals, win_hi, nkeys, nvals,
+      region_bits, out_keys, out_wins, out_vals, out_n, error_flag);
 }
 
 static void stats_insert_impl(
@@ -5303,35 +5501,14 @@ int64_t native_run_window_steps(
           using TSV =
               std::remove_const_t<std::remove_pointer_t<decltype(tsptr)>>;
           if (kind == SCAT_STAGED) {
-            int su = 16;
-            if (const char* e = std::getenv("BYTEWAX_SCATTER_U")) {
-              int v = atoi(e);
-              if (v == 8 || v == 16 || v == 32) su = v;
-            }
-            unsigned gs = (unsigned)((n + 256 * su - 1) / (256 * su));
-            if (gs > 1024) gs = 1024;
-            if (gs < 1) gs = 1;
-            auto launch_staged = [&](auto kern) {
-              hipLaunchKernelGGL(
-                  kern, dim3(gs), block,
-                  staged_lds, sc_stream, keys.data_ptr<int32_t>(),
-                  tsptr, (const int64_t*)nullptr, n,
-                  align_ms, len_ms, len_ms, base, mask, seg_bits, cap,
-                  gcur.data_ptr<int32_t>(), (uint64_t*)evp.data_ptr<int64_t>(),
-                  (int64_t*)nullptr, ovc.data_ptr<int32_t>(),
-                  (uint64_t*)ovp.data_ptr<int64_t>(), (int64_t*)nullptr,
-                  ovp.numel(),
-                  (unsigned long long*)max_ts.data_ptr<int64_t>(),
-                  error_flag.data_ptr<int32_t>(), win_m2, win_maxfast,
-                  NO_LATE_ARGS);
-            };
-            if (su == 8)
-              launch_staged(k_radix_scatter_staged<AGG_COUNT, TSV, 8>);
-            else if (su == 32)
-              launch_staged(k_radix_scatter_staged<AGG_COUNT, TSV, 32>);
-            else
-              launch_staged(k_radix_scatter_staged<AGG_COUNT, TSV, 16>);
-            // (pipe path keeps 256-thread blocks; serial is default)
+            launch_count_staged<TSV>(
+                sc_stream, keys.data_ptr<int32_t>(), tsptr, n, 1, align_ms,
+                len_ms, len_ms, base, mask, seg_bits, nseg, cap,
+                gcur.data_ptr<int32_t>(), (uint64_t*)evp.data_ptr<int64_t>(),
+                ovc.data_ptr<int32_t>(), (uint64_t*)ovp.data_ptr<int64_t>(),
+                ovp.numel(), (unsigned long long*)max_ts.data_ptr<int64_t>(),
+                error_flag.data_ptr<int32_t>(), win_m2, win_maxfast,
+            /*overlapped=*/true);
           } else if (kind == SCAT_DIRECT) {
             hipLaunchKernelGGL(
                 (k_radix_scatter_direct<AGG_COUNT, TSV>), grid, block, 0,
@@ -5416,16 +5593,9 @@ int64_t native_run_window_steps(
       int64_t horizon = (wm - wait_ms - align_ms) / len_ms;
       if (horizon > closed_horizon) {
         HIP_CHECK(hipMemsetAsync(out_n.data_ptr<int32_t>(), 0, sizeof(int), stream));
-        hipLaunchKernelGGL(
-            k_close_migrate, dim3(n_blocks(nslots, 256)), block, 0, stream,
-            (const uint64_t*)cur_k.data_ptr<int64_t>(),
-            (const unsigned long long*)cur_v.data_ptr<int64_t>(), nslots,
-            horizon, (uint64_t*)alt_k.data_ptr<int64_t>(),
-            (unsigned long long*)alt_v.data_ptr<int64_t>(),
-            (uint64_t)(nslots - 1), (int)region_bits,
-            out_keys.data_ptr<int32_t>(), out_wins.data_ptr<int32_t>(),
-            out_vals.data_ptr<int64_t>(), out_n.data_ptr<int32_t>(),
-            out_keys.numel(), error_flag.data_ptr<int32_t>());
+        launch_close_migrate(
+            stream, cur_k, cur_v, horizon, alt_k, alt_v, region_bits,
+            out_keys, out_wins, out_vals, out_n, error_flag);
         HIP_CHECK(hipMemcpyAsync(h_n, out_n.data_ptr<int32_t>(), sizeof(int),
                        hipMemcpyDeviceToHost, stream));
         std::swap(cur_k, alt_k);
@@ -5553,16 +5723,9 @@ int64_t native_run_window_steps_graph(
                                stream));
       // Migrate live cells out and back so the graph's captured table
       // pointers stay authoritative.
-      hipLaunchKernelGGL(
-          k_close_migrate, dim3(n_blocks(nslots, 256)), block, 0, stream,
-          (const uint64_t*)tkeys.data_ptr<int64_t>(),
-          (const unsigned long long*)tvals.data_ptr<int64_t>(), nslots,
-          horizon, (uint64_t*)alt_tkeys.data_ptr<int64_t>(),
-          (unsigned long long*)alt_tvals.data_ptr<int64_t>(), mask,
-          (int)region_bits, out_keys.data_ptr<int32_t>(),
-          out_wins.data_ptr<int32_t>(), out_vals.data_ptr<int64_t>(),
-          out_n.data_ptr<int32_t>(), out_keys.numel(),
-          error_flag.data_ptr<int32_t>());
+      launch_close_migrate(
+          stream, tkeys, tvals, horizon, alt_tkeys, alt_tvals, region_bits,
+          out_keys, out_wins, out_vals, out_n, error_flag);
       HIP_CHECK(hipMemcpyAsync(h_n, out_n.data_ptr<int32_t>(), sizeof(int),
                                hipMemcpyDeviceToHost, stream));
       // Reset the primary and migrate back (no emissions: horizon
@@ -5571,16 +5734,10 @@ int64_t native_run_window_steps_graph(
                                (size_t)nslots * 8, stream));
       HIP_CHECK(hipMemsetAsync(tvals.data_ptr<int64_t>(), 0,
                                (size_t)nslots * 8, stream));
-      hipLaunchKernelGGL(
-          k_close_migrate, dim3(n_blocks(nslots, 256)), block, 0, stream,
-          (const uint64_t*)alt_tkeys.data_ptr<int64_t>(),
-          (const unsigned long long*)alt_tvals.data_ptr<int64_t>(), nslots,
-          (int64_t)(-(1LL << 40)), (uint64_t*)tkeys.data_ptr<int64_t>(),
-          (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
-          (int)region_bits, out_keys.data_ptr<int32_t>(),
-          out_wins.data_ptr<int32_t>(), out_vals.data_ptr<int64_t>(),
-          out_n.data_ptr<int32_t>(), out_keys.numel(),
-          error_flag.data_ptr<int32_t>());
+      launch_close_migrate(
+          stream, alt_tkeys, alt_tvals, (int64_t)(-(1LL << 40)), tkeys,
+          tvals, region_bits, out_keys, out_wins, out_vals, out_n,
+          error_flag);
       HIP_CHECK(hipMemsetAsync(alt_tkeys.data_ptr<int64_t>(), 0xFF,
                                (size_t)nslots * 8, stream));
       HIP_CHECK(hipMemsetAsync(alt_tvals.data_ptr<int64_t>(), 0,
