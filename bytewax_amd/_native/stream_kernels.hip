@@ -1496,6 +1496,211 @@ __global__ __launch_bounds__(1024) void k_radix_agg(
   }
 }
 
+// Window deltas a compact cell can hold (the delta nibble 15 is left
+// to the empty marker), and where the segment's first window sits in
+// that range.
+#define AGG_DELTA_MAX 14u
+#define AGG_DELTA_MID 7u
+
+// COUNT segment aggregation with 8-byte LDS cells.
+//
+// Same contract as k_radix_agg<AGG_COUNT> (`ev_packed` / `counts` /
+// `cap`, head and tail peeling, EMPTY_SLOT pads, register double
+// buffer of 16-byte loads), half the LDS: a cell is
+//   key32 (high dword) | window delta (4 bits) | count (28 bits)
+// so the table of a 2^13-slot segment is 64 KiB and two workgroups
+// share a CU: one clears or flushes while the other streams.  The
+// delta is taken against a block-uniform base (the window of the
+// segment's first entry minus AGG_DELTA_MID) and restricted to
+// 0..AGG_DELTA_MAX, so no valid cell, whatever its key, equals the
+// all-ones empty marker; an entry outside that range goes straight to
+// the global table, which is exact.  A cell is claimed by a 64-bit CAS
+// of empty -> (key, delta, count 0) and counted with a 32-bit add on
+// the low dword; the host takes this kernel only when `cap` < 2^28, so
+// a count never carries into the delta.
+//
+// The first probe of a chunk's 2R entries is batched: all slot indices
+// are computed and all cells read before the first wait, and entries
+// whose cell already carries their tag add at once.  What is left (a
+// cell to claim, a collision, a window out of range) goes through ONE
+// probe / CAS loop per chunk, in which every lane works through its own
+// leftovers one probe step at a time.  A wave then waits for the LDS
+// about once per chunk plus once per probe step of its busiest lane,
+// where a probe loop per entry waits for the longest chain among 64
+// lanes 2R times over.
+template <int BLK, int R>
+__global__ __launch_bounds__(BLK, BLK == 1024 ? 8 : 4) void k_radix_agg_count(
+    const uint64_t* __restrict__ ev_packed,
+    const int* __restrict__ counts,
+    int64_t cap,
+    uint64_t* __restrict__ tkeys,
+    unsigned long long* __restrict__ tvals,
+    uint64_t mask,
+    int region_bits,
+    int lds_bits,
+    int* __restrict__ error_flag) {
+  extern __shared__ char smem[];
+  unsigned long long* cells = (unsigned long long*)smem;
+  const int region = 1 << lds_bits;
+  const uint32_t lmask = (uint32_t)region - 1;
+  const int b = blockIdx.x;
+  int cnt = counts[b];
+  if (cnt > (int)cap) cnt = (int)cap;
+  if (cnt <= 0) return;  // block-uniform
+  for (int s = threadIdx.x; s < region / 2; s += BLK) {
+    ((agg_u64x2*)cells)[s] = agg_u64x2{EMPTY_SLOT, EMPTY_SLOT};
+  }
+  const uint64_t* seg = ev_packed + (int64_t)b * cap;
+  // Any base is correct; this one puts the first entry's window in the
+  // middle of the range.
+  const uint32_t wbase = (uint32_t)(seg[0] >> 32) - AGG_DELTA_MID;
+  __syncthreads();
+
+  auto escape = [&](uint64_t packed) {
+    if (!hash_add(tkeys, tvals, mask, region_bits, packed, 1ULL)) {
+      atomicOr(error_flag, 1);
+    }
+  };
+  auto slot_of = [&](uint64_t packed) {
+    return (uint32_t)(mix64(packed) >> 32) & lmask;
+  };
+  // key | delta, as it stands in the upper 36 bits of a cell.
+  auto tag_of = [&](uint64_t packed) {
+    return ((unsigned long long)(uint32_t)packed << 4) |
+           (unsigned long long)((uint32_t)(packed >> 32) - wbase);
+  };
+  // Probe / claim loop over a lane's leftovers: the source of truth.
+  // `pend` has one bit per entry; `entry(e)` and `start(e)` give the
+  // packed value and the first slot to look at, `skipped(e)` says
+  // whether the entry's home slot has been ruled out already.
+  auto drain = [&](uint32_t pend, auto entry, auto start, auto skipped) {
+    uint64_t packed = 0;
+    unsigned long long tag = 0;
+    uint32_t lh = 0;
+    int left = 0;  // probe steps before the table counts as full
+    while (left != 0 || pend != 0) {
+      if (left == 0) {
+        int e = __ffs(pend) - 1;
+        pend &= pend - 1;
+        packed = entry(e);
+        if ((uint32_t)(packed >> 32) - wbase > AGG_DELTA_MAX) {
+          escape(packed);
+          continue;
+        }
+        tag = tag_of(packed);
+        lh = start(e);
+        left = region - (skipped(e) ? 1 : 0);
+      }
+      unsigned long long cur = cells[lh];
+      if (cur == EMPTY_SLOT) {
+        cur = atomicCAS(&cells[lh], EMPTY_SLOT, tag << 28);
+        if (cur == EMPTY_SLOT) cur = tag << 28;
+      }
+      if ((cur >> 28) == tag) {
+        atomicAdd((unsigned int*)&cells[lh], 1u);
+        left = 0;
+      } else {
+        lh = (lh + 1) & lmask;
+        if (--left == 0) escape(packed);  // LDS table full
+      }
+    }
+  };
+  auto add_one = [&](uint64_t packed) {
+    if (packed == EMPTY_SLOT) return;  // staged-scatter pad
+    drain(
+        1u, [&](int) { return packed; },
+        [&](int) { return slot_of(packed); }, [&](int) { return false; });
+  };
+
+  // Head/tail entries outside the 16-byte-aligned vector body.
+  const int head = ((uintptr_t)seg & 15) != 0 ? 1 : 0;
+  const int nvec = (cnt - head) >> 1;
+  const int tail = head + 2 * nvec;  // == cnt or cnt - 1
+  if (threadIdx.x == 0 && head) add_one(seg[0]);
+  if (threadIdx.x == BLK - 1 && tail < cnt) add_one(seg[tail]);
+
+  const agg_u64x2* vseg = (const agg_u64x2*)(seg + head);
+  constexpr int chunk = R * BLK;
+  constexpr int E = 2 * R;
+  agg_u64x2 cur_p[R], nxt_p[R];
+  auto fetch = [&](agg_u64x2 (&bp)[R], int base) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int v = base + r * BLK + (int)threadIdx.x;
+      if (v < nvec) bp[r] = vseg[v];
+      else bp[r] = agg_u64x2{EMPTY_SLOT, EMPTY_SLOT};
+    }
+  };
+  fetch(cur_p, 0);
+  for (int base = 0; base < nvec; base += chunk) {
+    // Issue the next chunk's loads before touching the LDS table.
+    if (base + chunk < nvec) fetch(nxt_p, base + chunk);
+    uint32_t slot[E];
+    unsigned long long first[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      uint64_t packed = (e & 1) ? cur_p[e >> 1].y : cur_p[e >> 1].x;
+      slot[e] = slot_of(packed);
+      first[e] = cells[slot[e]];
+    }
+    uint32_t pend = 0, moved = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      uint64_t packed = (e & 1) ? cur_p[e >> 1].y : cur_p[e >> 1].x;
+      if (packed == EMPTY_SLOT) continue;  // staged-scatter pad
+      bool in_range = (uint32_t)(packed >> 32) - wbase <= AGG_DELTA_MAX;
+      if (in_range && (first[e] >> 28) == tag_of(packed)) {
+        atomicAdd((unsigned int*)&cells[slot[e]], 1u);
+      } else {
+        pend |= 1u << e;
+        if (first[e] != EMPTY_SLOT) {
+          // Another cell's: start one further on.
+          slot[e] = (slot[e] + 1) & lmask;
+          moved |= 1u << e;
+        }
+      }
+    }
+    if (pend != 0) {
+      drain(
+          pend,
+          [&](int e) {
+            uint64_t v = 0;
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+              if (j == e) v = (j & 1) ? cur_p[j >> 1].y : cur_p[j >> 1].x;
+            }
+            return v;
+          },
+          [&](int e) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+              if (j == e) v = slot[j];
+            }
+            return v;
+          },
+          [&](int e) { return ((moved >> e) & 1u) != 0; });
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) cur_p[r] = nxt_p[r];
+  }
+  __syncthreads();
+
+  // Flush each cell once into its key's own table region (the
+  // segment's regions are contiguous in HBM, so flushes stay local).
+  for (int s = threadIdx.x; s < region; s += BLK) {
+    unsigned long long c = cells[s];
+    if (c != EMPTY_SLOT) {
+      uint64_t packed =
+          ((uint64_t)(wbase + ((uint32_t)c >> 28)) << 32) | (c >> 32);
+      if (!hash_add(tkeys, tvals, mask, region_bits, packed,
+                    c & 0x0FFFFFFFULL)) {
+        atomicOr(error_flag, 1);
+      }
+    }
+  }
+}
+
 // Overflow spill for the stats table (direct contended path).
 __global__ void k_overflow_agg_stats(
     const uint64_t* __restrict__ ov_packed,
@@ -3313,6 +3518,43 @@ static void launch_count_staged(
        NO_LATE_ARGS);
 }
 
+// BYTEWAX_AGG=wide selects the 16-byte-cell kernel for COUNT (A/B).
+static bool agg_wide_env() {
+  const char* s = std::getenv("BYTEWAX_AGG");
+  return s != nullptr && s[0] == 'w';
+}
+
+// The one place that picks and launches the COUNT segment aggregation
+// (radix_window_insert, radix_agg_only and the native step loop).
+// One workgroup per scatter segment; `seg_bits` is also the size of
+// its LDS table.  The compact-cell kernel holds a count in 28 bits, so
+// it is taken only when no segment can hold 2^28 entries.
+static void launch_count_agg(
+    hipStream_t stream, const uint64_t* evp, const int* gcur, int64_t cap,
+    uint64_t* tkeys, unsigned long long* tvals, uint64_t mask,
+    int region_bits, int seg_bits, int64_t nseg, int* err) {
+  auto go = [&](auto kern, int threads, size_t lds, auto... lead) {
+    hipLaunchKernelGGL(
+        kern, dim3((unsigned)nseg), dim3((unsigned)threads), lds, stream,
+        evp, lead..., gcur, cap, tkeys, tvals, mask, region_bits, seg_bits,
+        err);
+    // A refused launch (LDS budget, bad configuration) must not pass
+    // for an empty batch.
+    HIP_CHECK(hipGetLastError());
+  };
+  if (!agg_wide_env() && cap < ((int64_t)1 << 28) && seg_bits >= 8 &&
+      seg_bits <= 13) {
+    size_t lds = (size_t)8 << seg_bits;
+    // 1024 x 2: two workgroups per CU inside the 64-VGPR budget that
+    // leaves; R = 4 needs scratch there (see profiles/).
+    if (seg_bits >= 12) go((k_radix_agg_count<1024, 2>), 1024, lds);
+    else go((k_radix_agg_count<256, 2>), 256, lds);
+    return;
+  }
+  go(k_radix_agg<AGG_COUNT>, seg_bits >= 12 ? 1024 : 256,
+     (size_t)16 << seg_bits, (const int64_t*)nullptr);
+}
+
 static void radix_window_insert_impl(
     torch::Tensor keys,
     torch::Tensor ts,
@@ -3580,8 +3822,16 @@ static void radix_window_insert_impl(
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
         (int)region_bits, seg_bits, error_flag.data_ptr<int32_t>());
   };
-  if (mode == AGG_COUNT) agg(k_radix_agg<AGG_COUNT>);
-  else agg(k_radix_agg<AGG_SUM>);
+  if (mode == AGG_COUNT) {
+    launch_count_agg(
+        stream, (const uint64_t*)ev_packed.data_ptr<int64_t>(),
+        gcursors.data_ptr<int32_t>(), cap,
+        (uint64_t*)tkeys.data_ptr<int64_t>(),
+        (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
+        (int)region_bits, seg_bits, nseg, error_flag.data_ptr<int32_t>());
+  } else {
+    agg(k_radix_agg<AGG_SUM>);
+  }
 
   auto ov = [&](auto kern) {
     hipLaunchKernelGGL(
@@ -3905,8 +4155,16 @@ void radix_agg_only(
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
         (int)region_bits, seg_bits, error_flag.data_ptr<int32_t>());
   };
-  if (mode == AGG_COUNT) agg(k_radix_agg<AGG_COUNT>);
-  else agg(k_radix_agg<AGG_SUM>);
+  if (mode == AGG_COUNT) {
+    launch_count_agg(
+        stream, (const uint64_t*)ev_packed.data_ptr<int64_t>(),
+        gcursors.data_ptr<int32_t>(), cap,
+        (uint64_t*)tkeys.data_ptr<int64_t>(),
+        (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
+        (int)region_bits, seg_bits, nseg, error_flag.data_ptr<int32_t>());
+  } else {
+    agg(k_radix_agg<AGG_SUM>);
+  }
   auto ov = [&](auto kern) {
     hipLaunchKernelGGL(
         kern, dim3(64), dim3(256), 0, stream,
@@ -5542,15 +5800,13 @@ int64_t native_run_window_steps(
         else scat_step(ts.data_ptr<int64_t>());
         HIP_CHECK(hipEventRecord(ev_sc[par], sc_stream));
         HIP_CHECK(hipStreamWaitEvent(stream, ev_sc[par], 0));
-        size_t agg_lds = (size_t)16 << seg_bits;
-        dim3 agg_block(seg_bits >= 12 ? 1024 : 256);
-        hipLaunchKernelGGL(
-            k_radix_agg<AGG_COUNT>, dim3((unsigned)nseg), agg_block,
-            agg_lds, stream, (const uint64_t*)evp.data_ptr<int64_t>(),
-            (const int64_t*)nullptr, gcur.data_ptr<int32_t>(), cap,
+        launch_count_agg(
+            stream, (const uint64_t*)evp.data_ptr<int64_t>(),
+            gcur.data_ptr<int32_t>(), cap,
             (uint64_t*)cur_k.data_ptr<int64_t>(),
             (unsigned long long*)cur_v.data_ptr<int64_t>(), mask,
-            (int)region_bits, seg_bits, error_flag.data_ptr<int32_t>());
+            (int)region_bits, seg_bits, nseg,
+            error_flag.data_ptr<int32_t>());
         hipLaunchKernelGGL(
             k_overflow_agg<AGG_COUNT>, dim3(64), block, 0, stream,
             (const uint64_t*)ovp.data_ptr<int64_t>(),
