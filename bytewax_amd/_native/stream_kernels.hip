@@ -641,6 +641,56 @@ static inline void magic_div_u64(
   *maxfast = e ? (uint64_t)((one << p) / e) : ~(uint64_t)0;
 }
 
+// 32-bit window arithmetic for a launch of int32 deltas from one
+// host-known base (tumbling windows).  With a window id W chosen by the
+// host and c = ts_base - align_ms - W * len_ms, an event's window is
+// W + floor(y / len_ms), y = delta + c, whenever 0 <= y < 2^32 and the
+// event does not lie before align_ms (where win_of truncates towards
+// zero instead).  The host turns those conditions into one delta range
+// [dlo, dlo + dspan) and passes the round-up divider of Granlund and
+// Montgomery (1994, fig. 4.1), which is exact for every 32-bit
+// numerator and every divisor 1 <= len_ms < 2^32:
+//   t = mulhi(dm, y);  q = (t + ((y - t) >> sh1)) >> sh2.
+struct Win32 {
+  uint32_t dlo;    // first delta of the fast range
+  uint32_t dspan;  // its size; 0 sends every event to the generic path
+  uint32_t c;      // c mod 2^32
+  uint32_t wlo;    // W mod 2^32 (`packed` keeps 32 bits of the window)
+  uint32_t qoff;   // hashed entries store q - qoff (entry base W + qoff)
+  uint32_t dm;
+  int sh1, sh2;
+};
+
+__device__ __forceinline__ uint32_t win32_div(uint32_t y, const Win32& w) {
+  uint32_t t = __umulhi(w.dm, y);
+  return (t + ((y - t) >> w.sh1)) >> w.sh2;
+}
+
+// Hashed scatter entries, the second `ev_packed` format, written by
+// k_radix_scatter_staged2<.., true> and read by
+// k_radix_agg_count<.., .., true> only:
+//   bits 63..32  key32
+//   bits 31..13  window delta against the call's entry base (19 bits)
+//   bits 12..0   (mix64(packed) >> 32) & 0x1FFF
+// The aggregation takes its LDS slot from the low bits (its tables have
+// at most 2^13 slots) and never hashes an entry it can count in LDS.
+// The largest delta is not used, so no entry equals the all-ones pad.
+#define ENTRY_SLOT_BITS 13
+#define ENTRY_SLOT_MASK 0x1FFFull
+#define ENTRY_DELTA_MASK 0x7FFFFu
+#define ENTRY_DELTA_LIMIT 0x7FFFFu  // deltas 0 .. LIMIT - 1 are stored
+// "Classic entries" in place of an entry base.
+#define ENTRY_W_CLASSIC INT64_MIN
+
+__device__ __forceinline__ uint32_t entry_delta(uint64_t entry) {
+  return ((uint32_t)entry >> ENTRY_SLOT_BITS) & ENTRY_DELTA_MASK;
+}
+
+__device__ __forceinline__ uint64_t entry_classic(
+    uint64_t entry, uint32_t wlo) {
+  return ((uint64_t)(wlo + entry_delta(entry)) << 32) | (entry >> 32);
+}
+
 // TS is int64_t (absolute ms) or int32_t (deltas from `ts_base`, the
 // wire format of the RCCL exchange — inserting the received segments
 // directly skips the int64 timestamp rebuild entirely).
@@ -1138,7 +1188,21 @@ static inline size_t staged2_lds_bytes(int64_t nseg, int64_t tile) {
          + (stage_n / SC_GRAN) * sizeof(uint32_t);  // gdst
 }
 
-template <typename TS = int64_t, int U = 16, int BLK = 512>
+//
+// HASHED (int32 deltas from one host-known base only) writes hashed
+// entries (ENTRY_* above) for k_radix_agg_count<.., .., true>; the hash
+// that picks an event's segment also gives its entry the LDS slot.  In
+// this form P1 takes the window from the 32-bit arithmetic of Win32 and
+// issues its U histogram atomics unconditionally, as one batch.  An
+// event outside the host-proved delta range, or whose window does not
+// fit the 19-bit entry delta, is classified by the generic win_of in
+// one rare loop behind P1 and goes to the overflow spill, which holds
+// classic `packed` in either format (so does what the capacity split
+// sends there).  Measured at the bench shape, the 64-bit window code
+// and per-event atomic waits of the classic form cost the hashed kernel
+// 29 us of 368 (see profiles/r06_hashed_entries.md).
+template <typename TS = int64_t, int U = 16, int BLK = 512,
+          bool HASHED = false>
 __global__ __launch_bounds__(BLK) void k_radix_scatter_staged2(
     const int32_t* __restrict__ keys,
     const TS* __restrict__ ts,
@@ -1161,7 +1225,9 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged2(
     unsigned long long* __restrict__ max_ts,
     int* __restrict__ error_flag,
     uint64_t win_m2,
-    uint64_t win_maxfast) {
+    uint64_t win_maxfast,
+    Win32 w32) {  // HASHED only
+  static_assert(!HASHED || sizeof(TS) == 4, "hashed entries need deltas");
   constexpr int T = BLK * U;
   constexpr int NW = BLK / WAVE;
   // lpack: staging offset (14 bits) | residual count (3) | grant (14+).
@@ -1192,6 +1258,11 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged2(
     else atomicOr(error_flag, 1);
   };
 
+  // The spill holds classic `packed` whatever the entry format is.
+  auto classic_of = [&](uint64_t entry) {
+    return HASHED ? entry_classic(entry, w32.wlo + w32.qoff) : entry;
+  };
+
   // Raw columns of one tile, loaded a tile ahead.  The loads carry no
   // branch (the index is clamped, the lane is masked in P1): a branch
   // around each load makes U dependent round trips out of one batch,
@@ -1208,26 +1279,76 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged2(
     }
   };
   const int64_t stride = (int64_t)gridDim.x * T;
+  // Classic: maximum of the absolute timestamps.  Hashed: maximum of
+  // the int32 deltas (the base is added once at the end), starting from
+  // the lane's first event when it has one.
   int64_t local_max = 0;
   int64_t t0 = (int64_t)blockIdx.x * T;
-  if (t0 < n) load_tile(t0);
+  const bool seen = t0 + tid < n;
+  if (t0 < n) {
+    load_tile(t0);
+    if (HASHED) local_max = (int64_t)rt[0];
+  }
   for (; t0 < n; t0 += stride) {
     uint64_t pk[U];
-    int sr[U];  // (rank << 13) | segment, or -1 past the end
+    int sr[U];  // (rank << 13) | segment, or -1 when not placed
     // P1: classify, rank.
+    if (!HASHED) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      int64_t i = t0 + u * BLK + tid;
-      int64_t t = (int64_t)rt[u] + ts_base;
-      int64_t win = win_of(t, align_ms, len_ms, win_m2, win_maxfast);
-      uint64_t packed =
-          ((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)rk[u];
-      pk[u] = packed;
-      int b = (int)region_of(mix64(packed), mask, seg_bits);
-      sr[u] = -1;
-      if (i < n) {
-        if (t > local_max) local_max = t;
-        sr[u] = (atomicAdd(&lhist[b], 1) << 13) | b;
+      for (int u = 0; u < U; ++u) {
+        int64_t i = t0 + u * BLK + tid;
+        int64_t t = (int64_t)rt[u] + ts_base;
+        int64_t win = win_of(t, align_ms, len_ms, win_m2, win_maxfast);
+        uint64_t packed =
+            ((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)rk[u];
+        pk[u] = packed;
+        int b = (int)region_of(mix64(packed), mask, seg_bits);
+        sr[u] = -1;
+        if (i < n) {
+          if (t > local_max) local_max = t;
+          sr[u] = (atomicAdd(&lhist[b], 1) << 13) | b;
+        }
+      }
+    } else {
+      // Events of this tile that lane `tid` holds, in steps of BLK.
+      int64_t left64 = n - t0 - tid;
+      const int left = left64 > T ? T : (left64 < 0 ? 0 : (int)left64);
+      int32_t dmax = (int32_t)local_max;
+      uint32_t rare = 0;  // events for the generic path
+      // The histogram atomic is issued for every slot, with an
+      // increment of 0 for the ones that are not placed: inside a
+      // branch each of the U returning atomics is waited for on its
+      // own, unconditional they are one batch.
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const bool in = u * BLK < left;
+        const uint32_t d = (uint32_t)rt[u];
+        const uint32_t q = win32_div(d + w32.c, w32);
+        const uint64_t packed =
+            ((uint64_t)(w32.wlo + q) << 32) | (uint32_t)rk[u];
+        const uint64_t h64 = mix64(packed);
+        const uint32_t delta = q - w32.qoff;
+        const bool fits =
+            d - w32.dlo < w32.dspan && delta < ENTRY_DELTA_LIMIT;
+        pk[u] = ((uint64_t)(uint32_t)rk[u] << 32) |
+                (uint64_t)(delta << ENTRY_SLOT_BITS) |
+                ((h64 >> 32) & ENTRY_SLOT_MASK);
+        if (in && !fits) rare |= 1u << u;
+        if (in && (int32_t)d > dmax) dmax = (int32_t)d;
+        const bool ok = in && fits;
+        int b = (int)region_of(h64, mask, seg_bits);
+        int rank = atomicAdd(&lhist[b], ok ? 1 : 0);
+        sr[u] = ok ? ((rank << 13) | b) : -1;
+      }
+      local_max = dmax;
+      // Rare: one copy of the generic window code, columns read again.
+      while (rare != 0) {
+        int u = __ffs(rare) - 1;
+        rare &= rare - 1;
+        int64_t i = t0 + u * BLK + tid;
+        int64_t win = win_of((int64_t)ts[i] + ts_base, align_ms, len_ms,
+                             win_m2, win_maxfast);
+        spill(((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)keys[i]);
       }
     }
     if (t0 + stride < n) load_tile(t0 + stride);
@@ -1296,8 +1417,8 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged2(
       if (d != GD_SPILL) {
         *(ulonglong2*)(ev_packed + (int64_t)d * SC_GRAN + 2 * (p & 3)) = v;
       } else {
-        if (v.x != EMPTY_SLOT) spill(v.x);
-        if (v.y != EMPTY_SLOT) spill(v.y);
+        if (v.x != EMPTY_SLOT) spill(classic_of(v.x));
+        if (v.y != EMPTY_SLOT) spill(classic_of(v.y));
       }
     }
   }
@@ -1311,10 +1432,11 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged2(
         uint64_t p = j < rc ? res[(size_t)tid * SC_GRAN + j] : EMPTY_SLOT;
         int64_t gp = (int64_t)gb + j;
         if (gp < cap) ev_packed[(int64_t)tid * cap + gp] = p;
-        else if (p != EMPTY_SLOT) spill(p);
+        else if (p != EMPTY_SLOT) spill(classic_of(p));
       }
     }
   }
+  if (HASHED) local_max = seen ? local_max + ts_base : 0;
   for (int off = WAVE / 2; off > 0; off >>= 1) {
     int64_t other = __shfl_down((long long)local_max, off);
     if (other > local_max) local_max = other;
@@ -1528,7 +1650,12 @@ __global__ __launch_bounds__(1024) void k_radix_agg(
 // about once per chunk plus once per probe step of its busiest lane,
 // where a probe loop per entry waits for the longest chain among 64
 // lanes 2R times over.
-template <int BLK, int R>
+//
+// HASHED: the segment holds hashed entries (ENTRY_* above) against the
+// entry base whose low 32 bits are `wlo`.  The LDS slot is the entry's
+// low bits, the window delta its 19-bit field, and mix64 runs only in
+// hash_add, on the classic `packed` rebuilt for an escape or a flush.
+template <int BLK, int R, bool HASHED = false>
 __global__ __launch_bounds__(BLK, BLK == 1024 ? 8 : 4) void k_radix_agg_count(
     const uint64_t* __restrict__ ev_packed,
     const int* __restrict__ counts,
@@ -1538,7 +1665,8 @@ __global__ __launch_bounds__(BLK, BLK == 1024 ? 8 : 4) void k_radix_agg_count(
     uint64_t mask,
     int region_bits,
     int lds_bits,
-    int* __restrict__ error_flag) {
+    int* __restrict__ error_flag,
+    uint32_t wlo) {
   extern __shared__ char smem[];
   unsigned long long* cells = (unsigned long long*)smem;
   const int region = 1 << lds_bits;
@@ -1553,21 +1681,30 @@ __global__ __launch_bounds__(BLK, BLK == 1024 ? 8 : 4) void k_radix_agg_count(
   const uint64_t* seg = ev_packed + (int64_t)b * cap;
   // Any base is correct; this one puts the first entry's window in the
   // middle of the range.
-  const uint32_t wbase = (uint32_t)(seg[0] >> 32) - AGG_DELTA_MID;
+  // An entry's window (classic) or window delta (hashed), and its key.
+  auto win_part = [&](uint64_t packed) {
+    return HASHED ? entry_delta(packed) : (uint32_t)(packed >> 32);
+  };
+  auto key_part = [&](uint64_t packed) {
+    return HASHED ? (uint32_t)(packed >> 32) : (uint32_t)packed;
+  };
+  const uint32_t wbase = win_part(seg[0]) - AGG_DELTA_MID;
   __syncthreads();
 
   auto escape = [&](uint64_t packed) {
+    if (HASHED) packed = entry_classic(packed, wlo);
     if (!hash_add(tkeys, tvals, mask, region_bits, packed, 1ULL)) {
       atomicOr(error_flag, 1);
     }
   };
   auto slot_of = [&](uint64_t packed) {
+    if (HASHED) return (uint32_t)packed & lmask;
     return (uint32_t)(mix64(packed) >> 32) & lmask;
   };
   // key | delta, as it stands in the upper 36 bits of a cell.
   auto tag_of = [&](uint64_t packed) {
-    return ((unsigned long long)(uint32_t)packed << 4) |
-           (unsigned long long)((uint32_t)(packed >> 32) - wbase);
+    return ((unsigned long long)key_part(packed) << 4) |
+           (unsigned long long)(win_part(packed) - wbase);
   };
   // Probe / claim loop over a lane's leftovers: the source of truth.
   // `pend` has one bit per entry; `entry(e)` and `start(e)` give the
@@ -1583,7 +1720,7 @@ __global__ __launch_bounds__(BLK, BLK == 1024 ? 8 : 4) void k_radix_agg_count(
         int e = __ffs(pend) - 1;
         pend &= pend - 1;
         packed = entry(e);
-        if ((uint32_t)(packed >> 32) - wbase > AGG_DELTA_MAX) {
+        if (win_part(packed) - wbase > AGG_DELTA_MAX) {
           escape(packed);
           continue;
         }
@@ -1648,7 +1785,7 @@ __global__ __launch_bounds__(BLK, BLK == 1024 ? 8 : 4) void k_radix_agg_count(
     for (int e = 0; e < E; ++e) {
       uint64_t packed = (e & 1) ? cur_p[e >> 1].y : cur_p[e >> 1].x;
       if (packed == EMPTY_SLOT) continue;  // staged-scatter pad
-      bool in_range = (uint32_t)(packed >> 32) - wbase <= AGG_DELTA_MAX;
+      bool in_range = win_part(packed) - wbase <= AGG_DELTA_MAX;
       if (in_range && (first[e] >> 28) == tag_of(packed)) {
         atomicAdd((unsigned int*)&cells[slot[e]], 1u);
       } else {
@@ -1691,8 +1828,8 @@ __global__ __launch_bounds__(BLK, BLK == 1024 ? 8 : 4) void k_radix_agg_count(
   for (int s = threadIdx.x; s < region; s += BLK) {
     unsigned long long c = cells[s];
     if (c != EMPTY_SLOT) {
-      uint64_t packed =
-          ((uint64_t)(wbase + ((uint32_t)c >> 28)) << 32) | (c >> 32);
+      uint32_t win = wbase + ((uint32_t)c >> 28) + (HASHED ? wlo : 0u);
+      uint64_t packed = ((uint64_t)win << 32) | (c >> 32);
       if (!hash_add(tkeys, tvals, mask, region_bits, packed,
                     c & 0x0FFFFFFFULL)) {
         atomicOr(error_flag, 1);
@@ -3421,6 +3558,134 @@ static unsigned device_cu_count() {
   return (unsigned)cus;
 }
 
+// BYTEWAX_AGG=wide selects the 16-byte-cell kernel for COUNT (A/B).
+static bool agg_wide_env() {
+  const char* s = std::getenv("BYTEWAX_AGG");
+  return s != nullptr && s[0] == 'w';
+}
+
+// BYTEWAX_ENTRIES=classic keeps classic scatter entries (A/B, tests).
+static bool entries_classic_env() {
+  const char* s = std::getenv("BYTEWAX_ENTRIES");
+  return s != nullptr && s[0] == 'c';
+}
+
+// Launch shape of k_radix_scatter_staged2 for `nseg` segments; false
+// when the kernel cannot take them.
+static bool staged2_shape(int64_t nseg, int* threads, int* u, size_t* lds) {
+  int env_u = 0, env_threads = 0;
+  if (const char* e = std::getenv("BYTEWAX_SCATTER_U")) env_u = atoi(e);
+  if (const char* e = std::getenv("BYTEWAX_SCATTER_THREADS"))
+    env_threads = atoi(e);
+  *threads = env_threads == 1024 ? 1024 : 512;
+  *u = *threads == 512 && env_u != 8 ? 16 : 8;
+  *lds = staged2_lds_bytes(nseg, (int64_t)*threads * *u);
+  return nseg <= *threads && *lds <= 160 * 1024;
+}
+
+// Whether launch_count_staged takes staged2 (tumbling windows, the
+// kernel selected, its LDS fits, `ev_packed` 16-byte aligned).
+static bool count_staged2_ok(int64_t xf, const void* evp, int64_t nseg) {
+  int threads, u;
+  size_t lds;
+  return xf == 1 && scatter_staged2_env() && (((uintptr_t)evp) & 15) == 0 &&
+         staged2_shape(nseg, &threads, &u, &lds);
+}
+
+// Whether launch_count_agg takes the compact-cell kernel.
+static bool count_agg_compact(int64_t cap, int seg_bits) {
+  return !agg_wide_env() && cap < ((int64_t)1 << 28) && seg_bits >= 8 &&
+         seg_bits <= 13;
+}
+
+// What a COUNT scatter / aggregation pair agrees on for one scatter
+// call: the entry format and, for hashed entries, the bases and the
+// divider.  Every caller of launch_count_staged and launch_count_agg
+// plans here and hands the plan to both, so the two launches cannot
+// disagree.
+struct CountEntries {
+  bool hashed = false;
+  int64_t W = 0;      // window id that y = 0 of the first segment is in
+  uint32_t qoff = 0;  // entry base = W + qoff
+  uint32_t dm = 0;    // divider for len_ms
+  int sh1 = 0, sh2 = 0;
+  // What launch_count_agg is told: the entry base, or "classic".
+  int64_t agg_w() const {
+    return hashed ? W + (int64_t)qoff : ENTRY_W_CLASSIC;
+  }
+};
+
+// Hashed entries need: the staged2 scatter in its default tile shape,
+// the compact-cell aggregation, timestamps that are int32 deltas from a
+// host-known base, a window length Win32 can divide by (below 2^31 ms),
+// and no BYTEWAX_ENTRIES=classic.
+//
+// `staged_count`: the caller is about to call launch_count_staged
+// (staged kind, COUNT, no late tracking).  `first_base`: ts_base of the
+// call's first non-empty segment.  W lies 2^31 ms before it, rounded
+// down to a window, so that c of that segment is in [2^31, 2^31 +
+// len_ms) and nearly the whole int32 delta domain gives 0 <= y < 2^32.
+// The entry base lies 2^18 windows before the window of `first_base`
+// (but not before W), so the 19-bit entry delta reaches about as far
+// back as forward.
+static CountEntries plan_count_entries(
+    bool staged_count, int64_t xf, const void* evp, int64_t nseg,
+    int64_t cap, int seg_bits, bool ts_i32, int64_t align_ms,
+    int64_t len_ms, int64_t first_base) {
+  CountEntries ce;
+  if (!staged_count || !ts_i32 || entries_classic_env() ||
+      !count_staged2_ok(xf, evp, nseg) || !count_agg_compact(cap, seg_bits))
+    return ce;
+  if (len_ms < 1 || len_ms >= ((int64_t)1 << 31)) return ce;
+  // Built for the default tile shape only.
+  int threads, u;
+  size_t lds;
+  staged2_shape(nseg, &threads, &u, &lds);
+  if (threads != 512 || u != 16) return ce;
+  __int128 num = (__int128)first_base - align_ms - ((__int128)1 << 31);
+  __int128 w = num / len_ms;
+  if (num % len_ms < 0) w -= 1;  // floor
+  if (w < -((__int128)1 << 62) || w > ((__int128)1 << 62)) return ce;
+  ce.hashed = true;
+  ce.W = (int64_t)w;
+  int l = 0;
+  while (((int64_t)1 << l) < len_ms) ++l;
+  ce.dm = (uint32_t)((((unsigned __int128)1 << 32) *
+                      (uint64_t)(((int64_t)1 << l) - len_ms)) /
+                     (uint64_t)len_ms) + 1u;
+  ce.sh1 = l < 1 ? l : 1;
+  ce.sh2 = l > 1 ? l - 1 : 0;
+  int64_t q0 = (int64_t)((num - w * len_ms + ((__int128)1 << 31)) / len_ms);
+  ce.qoff = q0 > (1 << 18) ? (uint32_t)(q0 - (1 << 18)) : 0u;
+  return ce;
+}
+
+// Win32 of one launch with base `ts_base` under the call's entry base.
+static Win32 make_win32(
+    const CountEntries& ce, int64_t ts_base, int64_t align_ms,
+    int64_t len_ms) {
+  Win32 w{};
+  __int128 c = (__int128)ts_base - align_ms - (__int128)ce.W * len_ms;
+  __int128 lo = -((__int128)1 << 31), hi = ((__int128)1 << 31) - 1;
+  if (-c > lo) lo = -c;                                    // y >= 0
+  if ((__int128)align_ms - ts_base > lo) lo = (__int128)align_ms - ts_base;
+  __int128 top = ((__int128)1 << 32) - 1 - c;              // y < 2^32
+  if (top < hi) hi = top;
+  if (hi >= lo) {
+    __int128 span = hi - lo + 1;
+    if (span > 0xFFFFFFFFll) span = 0xFFFFFFFFll;
+    w.dlo = (uint32_t)(int32_t)(int64_t)lo;
+    w.dspan = (uint32_t)(uint64_t)span;
+  }
+  w.c = (uint32_t)(uint64_t)(c & 0xFFFFFFFFll);
+  w.wlo = (uint32_t)(uint64_t)ce.W;
+  w.qoff = ce.qoff;
+  w.dm = ce.dm;
+  w.sh1 = ce.sh1;
+  w.sh2 = ce.sh2;
+  return w;
+}
+
 // The one place that picks and launches the staged COUNT scatter
 // without late tracking (tumbling or sliding; `xf` is the sliding
 // expansion factor).  radix_window_insert, radix_scatter_only and the
@@ -3438,7 +3703,7 @@ static void launch_count_staged(
     int64_t ts_base, uint64_t mask, int seg_bits, int64_t nseg, int64_t cap,
     int* gcur, uint64_t* evp, int* ovc, uint64_t* ovp, int64_t ov_cap,
     unsigned long long* max_ts, int* err, uint64_t win_m2,
-    uint64_t win_maxfast, bool overlapped) {
+    uint64_t win_maxfast, bool overlapped, const CountEntries& ce) {
   int env_u = 0, env_threads = 0, env_blocks = 0;
   if (const char* e = std::getenv("BYTEWAX_SCATTER_U")) env_u = atoi(e);
   if (const char* e = std::getenv("BYTEWAX_SCATTER_THREADS"))
@@ -3464,7 +3729,10 @@ static void launch_count_staged(
     // for an empty batch.
     HIP_CHECK(hipGetLastError());
   };
-  if (xf == 1 && scatter_staged2_env() && (((uintptr_t)evp) & 15) == 0) {
+  // `ce` comes from plan_count_entries, which asked the same question.
+  TORCH_CHECK(!ce.hashed || count_staged2_ok(xf, evp, nseg),
+              "hashed entries planned for a scatter that is not staged2");
+  if (count_staged2_ok(xf, evp, nseg)) {
     // 512 x 16: one workgroup per CU (LDS-bound), 8192-event tiles.
     // 1024 x 8 keeps 16 waves per CU and measured 4 % faster alone
     // (325 against 338 us), but its 128-VGPR budget spills 12 bytes
@@ -3479,18 +3747,27 @@ static void launch_count_staged(
     // share a CU with this kernel's, so some blocks start late; two
     // blocks per CU halve the share a late block drags behind it.
     const unsigned cus = device_cu_count() * (overlapped ? 2u : 1u);
-    int threads = env_threads == 1024 ? 1024 : 512;
-    int u = threads == 512 && env_u != 8 ? 16 : 8;
-    size_t lds = staged2_lds_bytes(nseg, (int64_t)threads * u);
-    if (nseg <= threads && lds <= 160 * 1024) {
-      if (threads == 1024)
-        go((k_radix_scatter_staged2<TSV, 8, 1024>), 1024, 8, cus, lds);
-      else if (u == 16)
-        go((k_radix_scatter_staged2<TSV, 16, 512>), 512, 16, cus, lds);
-      else
-        go((k_radix_scatter_staged2<TSV, 8, 512>), 512, 8, cus, lds);
-      return;
+    int threads, u;
+    size_t lds;
+    staged2_shape(nseg, &threads, &u, &lds);
+    Win32 w32{};
+    if constexpr (sizeof(TSV) == 4) {
+      if (ce.hashed) {
+        // Planned for the default shape only.
+        w32 = make_win32(ce, ts_base, align_ms, len_ms);
+        go((k_radix_scatter_staged2<TSV, 16, 512, true>), 512, 16, cus, lds,
+           w32);
+        return;
+      }
     }
+    TORCH_CHECK(!ce.hashed, "hashed entries need int32 timestamp deltas");
+    if (threads == 1024)
+      go((k_radix_scatter_staged2<TSV, 8, 1024>), 1024, 8, cus, lds, w32);
+    else if (u == 16)
+      go((k_radix_scatter_staged2<TSV, 16, 512>), 512, 16, cus, lds, w32);
+    else
+      go((k_radix_scatter_staged2<TSV, 8, 512>), 512, 8, cus, lds, w32);
+    return;
   }
   // One tile = blockDim * U events; enough blocks to fill the chip at
   // the REGISTER-bounded occupancy (98 VGPRs: two 512-thread
@@ -3518,12 +3795,6 @@ static void launch_count_staged(
        NO_LATE_ARGS);
 }
 
-// BYTEWAX_AGG=wide selects the 16-byte-cell kernel for COUNT (A/B).
-static bool agg_wide_env() {
-  const char* s = std::getenv("BYTEWAX_AGG");
-  return s != nullptr && s[0] == 'w';
-}
-
 // The one place that picks and launches the COUNT segment aggregation
 // (radix_window_insert, radix_agg_only and the native step loop).
 // One workgroup per scatter segment; `seg_bits` is also the size of
@@ -3532,28 +3803,48 @@ static bool agg_wide_env() {
 static void launch_count_agg(
     hipStream_t stream, const uint64_t* evp, const int* gcur, int64_t cap,
     uint64_t* tkeys, unsigned long long* tvals, uint64_t mask,
-    int region_bits, int seg_bits, int64_t nseg, int* err) {
-  auto go = [&](auto kern, int threads, size_t lds, auto... lead) {
-    hipLaunchKernelGGL(
-        kern, dim3((unsigned)nseg), dim3((unsigned)threads), lds, stream,
-        evp, lead..., gcur, cap, tkeys, tvals, mask, region_bits, seg_bits,
-        err);
-    // A refused launch (LDS budget, bad configuration) must not pass
-    // for an empty batch.
-    HIP_CHECK(hipGetLastError());
-  };
-  if (!agg_wide_env() && cap < ((int64_t)1 << 28) && seg_bits >= 8 &&
-      seg_bits <= 13) {
-    size_t lds = (size_t)8 << seg_bits;
+    int region_bits, int seg_bits, int64_t nseg, int* err,
+    int64_t entry_w) {
+  // `entry_w`: CountEntries::agg_w() of the scatter call that filled
+  // `evp`: its entry base when the entries are hashed, else
+  // ENTRY_W_CLASSIC.
+  const bool hashed = entry_w != ENTRY_W_CLASSIC;
+  const uint32_t wlo = hashed ? (uint32_t)(uint64_t)entry_w : 0u;
+  if (count_agg_compact(cap, seg_bits)) {
+    auto go = [&](auto kern, int threads) {
+      hipLaunchKernelGGL(
+          kern, dim3((unsigned)nseg), dim3((unsigned)threads),
+          (size_t)8 << seg_bits, stream, evp, gcur, cap, tkeys, tvals, mask,
+          region_bits, seg_bits, err, wlo);
+      // A refused launch (LDS budget, bad configuration) must not pass
+      // for an empty batch.
+      HIP_CHECK(hipGetLastError());
+    };
     // 1024 x 2: two workgroups per CU inside the 64-VGPR budget that
     // leaves; R = 4 needs scratch there (see profiles/).
-    if (seg_bits >= 12) go((k_radix_agg_count<1024, 2>), 1024, lds);
-    else go((k_radix_agg_count<256, 2>), 256, lds);
+    if (seg_bits >= 12) {
+      if (hashed) go((k_radix_agg_count<1024, 2, true>), 1024);
+      else go((k_radix_agg_count<1024, 2>), 1024);
+    } else {
+      if (hashed) go((k_radix_agg_count<256, 2, true>), 256);
+      else go((k_radix_agg_count<256, 2>), 256);
+    }
     return;
   }
-  go(k_radix_agg<AGG_COUNT>, seg_bits >= 12 ? 1024 : 256,
-     (size_t)16 << seg_bits, (const int64_t*)nullptr);
+  // Only the compact kernel reads hashed entries.
+  TORCH_CHECK(!hashed, "hashed scatter entries need the compact aggregation");
+  hipLaunchKernelGGL(
+      k_radix_agg<AGG_COUNT>, dim3((unsigned)nseg),
+      dim3(seg_bits >= 12 ? 1024u : 256u), (size_t)16 << seg_bits, stream,
+      evp, (const int64_t*)nullptr, gcur, cap, tkeys, tvals, mask,
+      region_bits, seg_bits, err);
+  HIP_CHECK(hipGetLastError());
 }
+
+// k_overflow_agg is grid-stride: a block per CU drains a large spill
+// (a batch whose windows do not fit the entry delta) with the whole
+// chip and costs nothing when the spill is empty.
+static dim3 overflow_agg_grid() { return dim3(device_cu_count()); }
 
 static void radix_window_insert_impl(
     torch::Tensor keys,
@@ -3704,6 +3995,10 @@ static void radix_window_insert_impl(
 
   uint64_t win_m2, win_maxfast;
   magic_div_u64(off_ms, &win_m2, &win_maxfast);
+  const CountEntries ce = plan_count_entries(
+      kind == SCAT_STAGED && mode == AGG_COUNT && late == nullptr, xf,
+      ev_packed.data_ptr<int64_t>(), nseg, cap, seg_bits, seg32 || ts32,
+      align_ms, len_ms, segs[0].base);
   unsigned scat_threads = 256;
   // `extra`: the trailing late-tracking arguments of the staged and
   // fixed kernels.
@@ -3778,7 +4073,7 @@ static void radix_window_insert_impl(
             (uint64_t*)ov_packed.data_ptr<int64_t>(), ov_packed.numel(),
             (unsigned long long*)max_ts.data_ptr<int64_t>(),
             error_flag.data_ptr<int32_t>(), win_m2, win_maxfast,
-            /*overlapped=*/false);
+            /*overlapped=*/false, ce);
       } else {
         unsigned cap_gs = env_blocks > 0 ? (unsigned)env_blocks : 1024u;
         unsigned gs = (unsigned)((sg.n * xf + 256 * 16 - 1) / (256 * 16));
@@ -3828,14 +4123,15 @@ static void radix_window_insert_impl(
         gcursors.data_ptr<int32_t>(), cap,
         (uint64_t*)tkeys.data_ptr<int64_t>(),
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
-        (int)region_bits, seg_bits, nseg, error_flag.data_ptr<int32_t>());
+        (int)region_bits, seg_bits, nseg, error_flag.data_ptr<int32_t>(),
+        ce.agg_w());
   } else {
     agg(k_radix_agg<AGG_SUM>);
   }
 
   auto ov = [&](auto kern) {
     hipLaunchKernelGGL(
-        kern, dim3(64), dim3(256), 0, stream,
+        kern, overflow_agg_grid(), dim3(256), 0, stream,
         (const uint64_t*)ov_packed.data_ptr<int64_t>(),
         mode == AGG_SUM ? ov_vals.data_ptr<int64_t>() : nullptr,
         ov_cursor.data_ptr<int32_t>(), ov_packed.numel(),
@@ -3920,7 +4216,9 @@ void radix_window_insert_late(
 // fences, NCCL completion ordering) lives in Python with torch
 // events, which keeps it per-state and lets the exchange wait be
 // recorded on the side stream only.
-void radix_scatter_only(
+// Returns what radix_agg_only must be told about the entries: the
+// call's entry base when they are hashed, else ENTRY_W_CLASSIC.
+int64_t radix_scatter_only(
     torch::Tensor keys,
     torch::Tensor ts,
     c10::optional<torch::Tensor> vals,
@@ -4015,7 +4313,7 @@ void radix_scatter_only(
       gcursors.data_ptr<int32_t>(), 0, (size_t)nseg * sizeof(int), stream));
   HIP_CHECK(hipMemsetAsync(
       ov_cursor.data_ptr<int32_t>(), 0, sizeof(int), stream));
-  if (n == 0) return;
+  if (n == 0) return ENTRY_W_CLASSIC;
 
   struct Seg {
     int64_t off, n, base;
@@ -4030,6 +4328,11 @@ void radix_scatter_only(
   } else {
     segs.push_back({0, n, ts_base});
   }
+  if (segs.empty()) return ENTRY_W_CLASSIC;
+  const CountEntries ce = plan_count_entries(
+      kind == SCAT_STAGED && mode == AGG_COUNT, xf,
+      ev_packed.data_ptr<int64_t>(), nseg, cap, seg_bits, seg32 || ts32,
+      align_ms, len_ms, segs[0].base);
   unsigned scat_threads = 256;
   // `extra`: the trailing late-tracking arguments of the staged and
   // fixed kernels (always off on this path).
@@ -4062,7 +4365,7 @@ void radix_scatter_only(
             (uint64_t*)ov_packed.data_ptr<int64_t>(), ov_packed.numel(),
             (unsigned long long*)max_ts.data_ptr<int64_t>(),
             error_flag.data_ptr<int32_t>(), win_m2, win_maxfast,
-            /*overlapped=*/true);
+            /*overlapped=*/true, ce);
       } else {
         unsigned gs = (unsigned)((sg.n + 4095) / 4096);
         if (gs > 1024) gs = 1024;
@@ -4090,8 +4393,11 @@ void radix_scatter_only(
     if (seg32 || ts32) scat_any(ts.data_ptr<int32_t>(), sg);
     else scat_any(ts.data_ptr<int64_t>(), sg);
   }
+  return ce.agg_w();
 }
 
+// `entry_w`: what the radix_scatter_only call that filled these buffers
+// returned.
 void radix_agg_only(
     torch::Tensor tkeys,
     torch::Tensor tvals,
@@ -4103,7 +4409,8 @@ void radix_agg_only(
     torch::Tensor ov_packed,
     torch::Tensor ov_vals,
     int64_t mode,
-    int64_t region_bits) {
+    int64_t region_bits,
+    int64_t entry_w = ENTRY_W_CLASSIC) {
   int64_t nslots = tkeys.numel();
   int64_t nb = nslots >> region_bits;
   auto stream = at::hip::getCurrentHIPStream();
@@ -4161,13 +4468,14 @@ void radix_agg_only(
         gcursors.data_ptr<int32_t>(), cap,
         (uint64_t*)tkeys.data_ptr<int64_t>(),
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
-        (int)region_bits, seg_bits, nseg, error_flag.data_ptr<int32_t>());
+        (int)region_bits, seg_bits, nseg, error_flag.data_ptr<int32_t>(),
+        mode == AGG_COUNT ? entry_w : ENTRY_W_CLASSIC);
   } else {
     agg(k_radix_agg<AGG_SUM>);
   }
   auto ov = [&](auto kern) {
     hipLaunchKernelGGL(
-        kern, dim3(64), dim3(256), 0, stream,
+        kern, overflow_agg_grid(), dim3(256), 0, stream,
         (const uint64_t*)ov_packed.data_ptr<int64_t>(),
         mode == AGG_SUM ? ov_vals.data_ptr<int64_t>() : nullptr,
         ov_cursor.data_ptr<int32_t>(), ov_packed.numel(),
@@ -5755,6 +6063,11 @@ int64_t native_run_window_steps(
             sc_stream));
         HIP_CHECK(hipMemsetAsync(
             ovc.data_ptr<int32_t>(), 0, sizeof(int), sc_stream));
+        // One scatter call per step: its own entry base.
+        const CountEntries ce = plan_count_entries(
+            kind == SCAT_STAGED, 1, evp.data_ptr<int64_t>(), nseg, cap,
+            seg_bits, ts.scalar_type() == torch::kInt32, align_ms, len_ms,
+            base);
         auto scat_step = [&](auto tsptr) {
           using TSV =
               std::remove_const_t<std::remove_pointer_t<decltype(tsptr)>>;
@@ -5766,7 +6079,7 @@ int64_t native_run_window_steps(
                 ovc.data_ptr<int32_t>(), (uint64_t*)ovp.data_ptr<int64_t>(),
                 ovp.numel(), (unsigned long long*)max_ts.data_ptr<int64_t>(),
                 error_flag.data_ptr<int32_t>(), win_m2, win_maxfast,
-            /*overlapped=*/true);
+                /*overlapped=*/true, ce);
           } else if (kind == SCAT_DIRECT) {
             hipLaunchKernelGGL(
                 (k_radix_scatter_direct<AGG_COUNT, TSV>), grid, block, 0,
@@ -5806,9 +6119,9 @@ int64_t native_run_window_steps(
             (uint64_t*)cur_k.data_ptr<int64_t>(),
             (unsigned long long*)cur_v.data_ptr<int64_t>(), mask,
             (int)region_bits, seg_bits, nseg,
-            error_flag.data_ptr<int32_t>());
+            error_flag.data_ptr<int32_t>(), ce.agg_w());
         hipLaunchKernelGGL(
-            k_overflow_agg<AGG_COUNT>, dim3(64), block, 0, stream,
+            k_overflow_agg<AGG_COUNT>, overflow_agg_grid(), block, 0, stream,
             (const uint64_t*)ovp.data_ptr<int64_t>(),
             (const int64_t*)nullptr, ovc.data_ptr<int32_t>(), ovp.numel(),
             (uint64_t*)cur_k.data_ptr<int64_t>(),
@@ -6316,9 +6629,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Experimental two-level radix with full-line LDS-staged "
         "scatter (COUNT mode)");
   m.def("radix_scatter_only", &radix_scatter_only,
-        "Scatter stage of the radix insert on the current stream");
+        "Scatter stage of the radix insert on the current stream; returns "
+        "the entry base for radix_agg_only");
   m.def("radix_agg_only", &radix_agg_only,
-        "Aggregation stage of the radix insert on the current stream");
+        "Aggregation stage of the radix insert on the current stream",
+        pybind11::arg("tkeys"), pybind11::arg("tvals"),
+        pybind11::arg("error_flag"), pybind11::arg("gcursors"),
+        pybind11::arg("ev_packed"), pybind11::arg("ev_vals"),
+        pybind11::arg("ov_cursor"), pybind11::arg("ov_packed"),
+        pybind11::arg("ov_vals"), pybind11::arg("mode"),
+        pybind11::arg("region_bits"),
+        pybind11::arg("entry_w") = (int64_t)ENTRY_W_CLASSIC);
   m.def("window_agg_insert_late", &window_agg_insert_late,
         "Single-pass window insert that diverts events below the late "
         "cutoff to a late buffer");

@@ -863,6 +863,10 @@ class WindowAggState:
         self._sc_stream = torch.cuda.Stream(self.device)
         self._pipe_parity = 0
         self._ev_sc = [torch.cuda.Event(), torch.cuda.Event()]
+        # What each parity's scatter said about its entries (the entry
+        # base of hashed entries, or the "classic" marker): host-known,
+        # so the aggregation needs no device word and no sync.
+        self._ev_w = [None, None]
         self._ev_ag = [torch.cuda.Event(), torch.cuda.Event()]
         self._ag_recorded = [False, False]
         if not hasattr(self, "rx_packed2"):
@@ -937,7 +941,7 @@ class WindowAggState:
             ts.record_stream(self._sc_stream)
             if vals is not None:
                 vals.record_stream(self._sc_stream)
-            self.k.radix_scatter_only(
+            self._ev_w[par] = self.k.radix_scatter_only(
                 keys,
                 ts,
                 vals,
@@ -963,6 +967,7 @@ class WindowAggState:
             *bufs,
             self.mode,
             self.region_bits,
+            self._ev_w[par],
         )
         self._ev_ag[par].record(cur)
         self._ag_recorded[par] = True
