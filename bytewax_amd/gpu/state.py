@@ -22,6 +22,11 @@ _I64_MAX = (1 << 63) - 1
 _I64_MIN = -(1 << 63)
 
 
+def _wrap64(x: int) -> int:
+    """Two's-complement int64 wrap, as the device's 64-bit adds do."""
+    return ((x + (1 << 63)) & ((1 << 64) - 1)) - (1 << 63)
+
+
 class StatsAggState:
     """Keyed (windowed) running count/sum/min/max on device.
 
@@ -250,7 +255,7 @@ class StatsAggState:
                 (k, w), (0, 0, _I64_MAX, _I64_MIN)
             )
             self._table[(k, w)] = (
-                cnt + 1, s + v, min(mn, v), max(mx, v)
+                cnt + 1, _wrap64(s + v), min(mn, v), max(mx, v)
             )
         if len(batch):
             mx_ts = int(batch.ts.max().item()) + batch.ts_base
@@ -375,7 +380,7 @@ class StatsAggState:
                 else:
                     self._table[kw] = (
                         cur[0] + c,
-                        cur[1] + s,
+                        _wrap64(cur[1] + s),
                         min(cur[2], mn),
                         max(cur[3], mx),
                     )
@@ -450,6 +455,7 @@ class HashJoinState:
         self.cpu = device.type == "cpu"
         if self.cpu:
             self._table: Dict[int, list] = {}
+            self._rows: List[Tuple[int, int, int]] = []
             return
         self.k = ext()
         if radix:
@@ -488,10 +494,18 @@ class HashJoinState:
         """Insert one side's (keys, vals) columns; completed pairs
         accumulate in the output buffer until `take_joined`."""
         if self.cpu:
+            # Per-event twin of `join_apply`: the event that makes both
+            # sides present emits the row and clears the flags, so a
+            # later duplicate of the key in the same batch re-arms its
+            # side.  Completing here, not in `take_joined`, keeps
+            # several inserts before one drain equal to the device.
             for k, v in zip(keys.tolist(), vals.tolist()):
                 ent = self._table.setdefault(int(k), [None, None, 0])
                 ent[side] = int(v)
                 ent[2] |= 1 << side
+                if ent[2] == 3:
+                    self._rows.append((int(k), ent[0], ent[1]))
+                    ent[2] = 0
             return
         if self.radix:
             import torch
@@ -629,11 +643,7 @@ class HashJoinState:
         import torch
 
         if self.cpu:
-            out = []
-            for k, ent in self._table.items():
-                if ent[2] == 3:
-                    out.append((k, ent[0], ent[1]))
-                    ent[2] = 0
+            out, self._rows = self._rows, []
             if not out:
                 return None
             return (
