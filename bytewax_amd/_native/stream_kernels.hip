@@ -3147,10 +3147,16 @@ __global__ void k_bucket_scatter(
 // Exactness: the device table stores the full 128-bit hash (lo is
 // the CAS claim word, hi the published check word).  Newly created
 // ids are read back as (id, batch_index) pairs so the host keeps the
-// authoritative id->string list; the Python layer verifies each new
-// id against its own exact dict and fails loudly on a 128-bit
-// collision (probability ~1e-26 at 1e6 keys) instead of aggregating
-// wrong.
+// authoritative id->string list.  Key identity on the device path IS
+// 128-bit hash equality: nothing compares string bytes, so two
+// strings with equal (lo, hi) would share an id silently
+// (probability ~1e-26 at 1e6 keys).  Two strings with equal lo only
+// are told apart by hi: the second one never finds a slot of its own
+// and surfaces as DICT_ERR_MISS.
+//
+// Errors are a bit set in `error_flag`, every bit set with atomicOr so
+// that none overwrites another (bytewax_amd/gpu/strings.py reports
+// them by priority: a full table also makes the lookup miss).
 //
 // Race-free without spins: insert and lookup are SEPARATE kernel
 // launches.  k_dict_insert only guarantees every distinct string has
@@ -3159,6 +3165,12 @@ __global__ void k_bucket_scatter(
 // globally visible at the kernel boundary).  k_dict_lookup then
 // resolves every event's id with plain loads.
 // ---------------------------------------------------------------------------
+
+// `error_flag` bits of the dictionary kernels (DICT_ERR_* in
+// bytewax_amd/gpu/strings.py).
+#define DICT_ERR_FULL 1    // no free slot left for a new string
+#define DICT_ERR_MISS 2    // lookup found no published (lo, hi) cell
+#define DICT_ERR_NEWCAP 4  // more new ids than the readback buffer holds
 
 __device__ __forceinline__ void str_hash128(
     const uint8_t* __restrict__ s, int len, uint64_t* h_lo,
@@ -3211,14 +3223,14 @@ __global__ void k_dict_insert(
             new_ids[r] = id;
             new_idx[r] = (int32_t)i;
           } else {
-            atomicExch(error_flag, 3);  // readback buffer overflow
+            atomicOr(error_flag, DICT_ERR_NEWCAP);
           }
           break;
         }
         if (prev == lo) break;
       }
       h = (h + 1) & mask;
-      if (probes == mask) atomicOr(error_flag, 1);  // table full
+      if (probes == mask) atomicOr(error_flag, DICT_ERR_FULL);
     }
   }
 }
@@ -3251,7 +3263,7 @@ __global__ void k_dict_lookup(
       h = (h + 1) & mask;
     }
     out_ids[i] = id;
-    if (id < 0) atomicExch(error_flag, 2);  // unpublished / collision
+    if (id < 0) atomicOr(error_flag, DICT_ERR_MISS);
   }
 }
 
@@ -3283,7 +3295,7 @@ __global__ void k_dict_insert_pinned(
         break;
       }
       h = (h + 1) & mask;
-      if (probes == mask) atomicOr(error_flag, 1);
+      if (probes == mask) atomicOr(error_flag, DICT_ERR_FULL);
     }
   }
 }

@@ -66,30 +66,50 @@ class RecordBatch:
         return int(self.keys.numel())
 
 
-def _mix64_torch(x):
-    """splitmix64 finalizer on int64 tensors, bit-identical to the
-    device `mix64` (logical shifts emulated by masking the arithmetic
-    shift's sign extension; multiplication wraps in both)."""
+def _mix64_np(x):
+    """The device `mix64` (splitmix64 finalizer) on a numpy uint64
+    array; unsigned arithmetic wraps exactly like the kernels'."""
+    import numpy as np
 
-    def shr(v, s):
-        return (v >> s) & ((1 << (64 - s)) - 1)
-
-    x = x ^ shr(x, 33)
-    x = x * -48064316817838067  # 0xff51afd7ed558ccd as int64
-    x = x ^ shr(x, 33)
-    x = x * -4265267296055464877  # 0xc4ceb9fe1a85ec53 as int64
-    x = x ^ shr(x, 33)
+    x = x ^ (x >> np.uint64(33))
+    x = x * np.uint64(0xFF51AFD7ED558CCD)
+    x = x ^ (x >> np.uint64(33))
+    x = x * np.uint64(0xC4CEB9FE1A85EC53)
+    x = x ^ (x >> np.uint64(33))
     return x
 
 
-def _bucket_cpu(batch: RecordBatch, world: int):
-    """Host twin of the bucketing kernels (power-of-two worlds match
-    the device hash exactly)."""
+def key_owner(keys, world: int):
+    """Owning rank of every int32 key: the bucketing kernels'
+    ``mix64((uint32_t)key) % (uint64_t)world`` exactly, for any
+    ``world >= 1`` and any int32 key (negative keys zero-extend, the
+    modulo is unsigned).  The device is the definition; this is its
+    host twin for the CPU path and for control-plane decisions that
+    must agree with where the kernels route live events.
+
+    :arg keys: int32 tensor (any device; the hash runs on the host).
+    :returns: int64 CPU tensor of ranks in ``[0, world)``.
+    """
+    import numpy as np
     import torch
 
-    dst = torch.remainder(
-        _mix64_torch(batch.keys.to(torch.int64)), world
-    )
+    if world < 1:
+        msg = f"world must be >= 1, got {world}"
+        raise ValueError(msg)
+    if keys.dtype != torch.int32:
+        msg = f"key_owner takes int32 keys, got {keys.dtype}"
+        raise TypeError(msg)
+    k = keys.detach().cpu().contiguous().numpy()
+    h = _mix64_np(k.view(np.uint32).astype(np.uint64))
+    return torch.from_numpy((h % np.uint64(world)).astype(np.int64))
+
+
+def _bucket_cpu(batch: RecordBatch, world: int):
+    """Host twin of the bucketing kernels: same owners for every
+    world, stable order within a destination."""
+    import torch
+
+    dst = key_owner(batch.keys, world)
     order = torch.argsort(dst, stable=True)
     counts = torch.bincount(dst, minlength=world).to(torch.int32)
     send_keys = batch.keys[order]

@@ -851,7 +851,7 @@ class _DeviceStatsLogic(StatefulBatchLogic):
         import numpy as np
         import torch
 
-        from . import _mix64_torch
+        from . import key_owner
 
         rows = []
         max_ts = None
@@ -886,10 +886,9 @@ class _DeviceStatsLogic(StatefulBatchLogic):
             for g in gathered:
                 if g is None:
                     continue
-                keys_t = torch.as_tensor(g["keys"]).to(torch.int64)
-                mine = (
-                    torch.remainder(_mix64_torch(keys_t), world) == rank
-                ).numpy()
+                # Same owner as the exchange kernels give live events.
+                keys_t = torch.as_tensor(g["keys"]).to(torch.int32)
+                mine = (key_owner(keys_t, world) == rank).numpy()
                 if mine.any():
                     parts.append({c: g[c][mine] for c in _STATS_COLS})
             merged = (

@@ -22,6 +22,28 @@ from ._ext import ext
 
 StrBatch = Union[Sequence[str], Tuple[np.ndarray, np.ndarray]]
 
+#: Bits of the dictionary kernels' `error_flag` (DICT_ERR_* in
+#: stream_kernels.hip).  Several can be set by one batch: a string that
+#: found no free slot is also missed by the lookup.
+DICT_ERR_FULL = 1
+DICT_ERR_MISS = 2
+DICT_ERR_NEWCAP = 4
+
+
+def _dict_error(flag: int) -> str:
+    """Message for a non-zero flag, by priority: the cause (full
+    table, then readback overflow) before its consequence (miss)."""
+    if flag & DICT_ERR_FULL:
+        return "string dictionary table full; increase slots_pow"
+    if flag & DICT_ERR_NEWCAP:
+        return "too many new keys in one batch; increase new_cap"
+    if flag & DICT_ERR_MISS:
+        return (
+            "string dictionary lookup failed (128-bit hash collision "
+            "or table anomaly)"
+        )
+    return f"string dictionary error {flag}"
+
 
 def pack_strings(strings: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
     """Pack python strings into (uint8 bytes, int64 offsets[n+1])."""
@@ -49,6 +71,55 @@ def _mix64(x: int) -> int:
     x = (x ^ (x >> 33)) & m
     x = (x * 0xC4CEB9FE1A85EC53) & m
     return (x ^ (x >> 33)) & m
+
+
+def _str_bucket_cpu(data_np, offs_np, ts_np, vals_np, world: int):
+    """Host twin of `str_exchange_pack`: `(counts, byte_counts,
+    send_lens, send_ts, send_vals, send_bytes)` in bucket-major wire
+    order (input order within a destination)."""
+    import torch
+
+    n = len(offs_np) - 1
+    buckets = [[] for _ in range(world)]
+    for i in range(n):
+        b = bytes(data_np[offs_np[i] : offs_np[i + 1]])
+        buckets[str_owner_cpu(b, world)].append(i)
+    send_lens, send_ts, send_vals, send_bytes = [], [], [], []
+    counts = []
+    for idxs in buckets:
+        counts.append(len(idxs))
+        for i in idxs:
+            send_lens.append(int(offs_np[i + 1] - offs_np[i]))
+            send_ts.append(int(ts_np[i]))
+            if vals_np is not None:
+                send_vals.append(int(vals_np[i]))
+            send_bytes.append(
+                data_np[offs_np[i] : offs_np[i + 1]].tobytes()
+            )
+    byte_counts = []
+    k = 0
+    for c in counts:
+        byte_counts.append(sum(send_lens[k : k + c]))
+        k += c
+    t_vals = (
+        torch.tensor(send_vals, dtype=torch.int64)
+        if vals_np is not None
+        else None
+    )
+    joined = b"".join(send_bytes)
+    t_bytes = (
+        torch.frombuffer(bytearray(joined), dtype=torch.uint8)
+        if joined
+        else torch.empty(0, dtype=torch.uint8)
+    )
+    return (
+        torch.tensor(counts, dtype=torch.int32),
+        torch.tensor(byte_counts, dtype=torch.int64),
+        torch.tensor(send_lens, dtype=torch.int32),
+        torch.tensor(send_ts, dtype=torch.int64),
+        t_vals,
+        t_bytes,
+    )
 
 
 def exchange_str_by_key(
@@ -87,42 +158,8 @@ def exchange_str_by_key(
             vals_np = np.asarray(
                 vals.numpy() if hasattr(vals, "numpy") else vals
             )
-        n = len(offs_np) - 1
-        buckets = [[] for _ in range(world)]
-        for i in range(n):
-            b = bytes(data_np[offs_np[i] : offs_np[i + 1]])
-            buckets[str_owner_cpu(b, world)].append(i)
-        send_lens, send_ts, send_vals, send_bytes = [], [], [], []
-        counts = []
-        for idxs in buckets:
-            counts.append(len(idxs))
-            for i in idxs:
-                send_lens.append(int(offs_np[i + 1] - offs_np[i]))
-                send_ts.append(int(ts_np[i]))
-                if vals_np is not None:
-                    send_vals.append(int(vals_np[i]))
-                send_bytes.append(
-                    data_np[offs_np[i] : offs_np[i + 1]].tobytes()
-                )
-        byte_counts = []
-        k = 0
-        for c in counts:
-            byte_counts.append(sum(send_lens[k : k + c]))
-            k += c
-        t_counts = torch.tensor(counts, dtype=torch.int32)
-        t_bcounts = torch.tensor(byte_counts, dtype=torch.int64)
-        t_lens = torch.tensor(send_lens, dtype=torch.int32)
-        t_ts = torch.tensor(send_ts, dtype=torch.int64)
-        t_vals = (
-            torch.tensor(send_vals, dtype=torch.int64)
-            if vals_np is not None
-            else None
-        )
-        joined = b"".join(send_bytes)
-        t_bytes = (
-            torch.frombuffer(bytearray(joined), dtype=torch.uint8)
-            if joined
-            else torch.empty(0, dtype=torch.uint8)
+        t_counts, t_bcounts, t_lens, t_ts, t_vals, t_bytes = (
+            _str_bucket_cpu(data_np, offs_np, ts_np, vals_np, world)
         )
     else:
         k = _ext_mod()
@@ -311,15 +348,9 @@ class StringDict:
             self.error_flag,
         )
         n_new = int(self.new_n.item())
-        if int(self.error_flag.item()) != 0:
-            code = int(self.error_flag.item())
-            msg = {
-                1: "string dictionary table full; increase slots_pow",
-                2: "string dictionary lookup failed (128-bit hash "
-                   "collision or table anomaly)",
-                3: "too many new keys in one batch; increase new_cap",
-            }.get(code, f"string dictionary error {code}")
-            raise RuntimeError(msg)
+        flag = int(self.error_flag.item())
+        if flag != 0:
+            raise RuntimeError(_dict_error(flag))
         if n_new:
             if data is None:
                 # Device-tensor input: fetch host bytes only when the
@@ -398,6 +429,7 @@ class StringDict:
             self.dlo, self.dhi, self.dids, self.error_flag,
         )
         self.counter.fill_(len(strings))
-        if int(self.error_flag.item()) != 0:
-            msg = "string dictionary restore failed (table full?)"
+        flag = int(self.error_flag.item())
+        if flag != 0:
+            msg = f"string dictionary restore failed: {_dict_error(flag)}"
             raise RuntimeError(msg)

@@ -24,14 +24,14 @@ if REPO not in sys.path:
 
 def expected(world: int):
     """What every rank together should hold after the exchange."""
-    from bytewax_amd.gpu import RecordBatch, _mix64_torch
+    from bytewax_amd.gpu import key_owner
 
     per = {}
     for rank in range(world):
         g = torch.Generator().manual_seed(1234 + rank)
         keys = torch.randint(0, 1000, (4096,), dtype=torch.int32, generator=g)
         ts = torch.arange(4096, dtype=torch.int64) + rank
-        dst = torch.remainder(_mix64_torch(keys.to(torch.int64)), world)
+        dst = key_owner(keys, world)
         for d in range(world):
             m = dst == d
             k, t = keys[m], ts[m]

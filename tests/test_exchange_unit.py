@@ -41,8 +41,8 @@ ra = sorted(zip(a.keys.tolist(), a.ts.tolist()))
 rb = sorted(zip(b.keys.tolist(), b.ts.tolist()))
 assert ra == rb, "ts_base fold mismatch"
 # Every received key must hash-route to this rank.
-from bytewax_amd.gpu import _mix64_torch
-owners = torch.remainder(_mix64_torch(a.keys.to(torch.int64)), 2)
+from bytewax_amd.gpu import key_owner
+owners = key_owner(a.keys, 2)
 assert bool((owners == rank).all()), "routing violated"
 t = torch.tensor([len(ra)], dtype=torch.int64)
 dist.all_reduce(t)
