@@ -2311,6 +2311,141 @@ __global__ void k_stats_extract(
   }
 }
 
+// Stats window close with reclamation: the count/sum/min/max twin of
+// k_close_migrate.  One pass over the table in CM_CHUNK-slot chunks
+// sorts every cell by its window id `w`:
+//   win_lo <= w < win_hi  emit the six columns;
+//   w >= win_hi           migrate into the fresh table;
+//   w < win_lo            drop.  Such a cell was made by an event
+//                         behind the watermark on a path that does not
+//                         track lateness, after its window had been
+//                         emitted; no extract ever reads it, so
+//                         dropping it changes no output.
+// The caller swaps the five arrays afterwards and resets the retired
+// ones (keys EMPTY, cnt/sum 0, min I64_MAX, max I64_MIN).
+//
+// Keys are loaded 16 bytes per lane and stay in registers; the four
+// value arrays (32 bytes per slot) are read only for a slot that is
+// emitted or migrated, at the point where it is, so a thread never
+// holds CM_PER x 4 values.  Output rows are reserved as in
+// k_close_migrate: wave scan, cross-wave LDS step, one
+// `atomicAdd(out_n, chunk_total)` by thread 0; rows past `cap` are
+// counted, not written.
+//
+// Migration stores the four values plainly after `find_slot` has
+// claimed the slot (every stats writer uses the whole-table layout).
+// The exactness argument of k_close_migrate holds unchanged: (1) the
+// target is fresh and each migrated cell is unique, so exactly one
+// thread of this kernel claims a given slot and nobody else touches
+// its values; (2) nothing else writes the target while the kernel
+// runs: every writer of either table (the stats insert, radix insert
+// and fixup kernels, the resets of the retired arrays) is enqueued on
+// the same stream as the close.  The stats insert has no side stream
+// at all.
+__global__ __launch_bounds__(CM_BLK) void k_stats_close_migrate(
+    const uint64_t* __restrict__ tkeys,
+    const long long* __restrict__ tcnt,
+    const long long* __restrict__ tsum,
+    const long long* __restrict__ tmin,
+    const long long* __restrict__ tmax,
+    int64_t nslots,
+    int64_t win_lo,
+    int64_t win_hi,
+    uint64_t* __restrict__ nkeys,
+    long long* __restrict__ ncnt,
+    long long* __restrict__ nsum,
+    long long* __restrict__ nmin,
+    long long* __restrict__ nmax,
+    uint64_t mask,
+    int32_t* __restrict__ out_keys,
+    int32_t* __restrict__ out_wins,
+    int64_t* __restrict__ out_cnt,
+    int64_t* __restrict__ out_sum,
+    int64_t* __restrict__ out_min,
+    int64_t* __restrict__ out_max,
+    int* __restrict__ out_n,
+    int64_t cap,
+    int* __restrict__ error_flag) {
+  constexpr int NW = CM_BLK / WAVE;
+  // Double-buffered by chunk parity: two barriers per chunk suffice.
+  __shared__ int s_wave[2][NW];
+  __shared__ int s_base[2];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const bool vec = (((uintptr_t)tkeys) & 15) == 0;
+  const int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  int par = 0;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x, par ^= 1) {
+    // Slot of k[q]: s0 + (q / 2) * (CM_BLK * 2) + (q & 1).
+    const int64_t s0 = c * CM_CHUNK + threadIdx.x * 2;
+    uint64_t k[CM_PER];
+    for (int j = 0; j < CM_PER / 2; ++j) {
+      int64_t s = s0 + (int64_t)j * (CM_BLK * 2);
+      if (vec && s + 1 < nslots) {
+        ulonglong2 kk = *(const ulonglong2*)(tkeys + s);
+        k[2 * j] = kk.x;
+        k[2 * j + 1] = kk.y;
+      } else {
+        for (int q = 0; q < 2; ++q) {
+          k[2 * j + q] = s + q < nslots ? tkeys[s + q] : EMPTY_SLOT;
+        }
+      }
+    }
+    unsigned takem = 0;
+    for (int q = 0; q < CM_PER; ++q) {
+      if (k[q] == EMPTY_SLOT) continue;
+      int64_t win = (int64_t)(int32_t)(uint32_t)(k[q] >> 32);
+      if (win < win_lo) continue;
+      if (win < win_hi) {
+        takem |= 1u << q;
+      } else {
+        int64_t s = s0 + (int64_t)(q >> 1) * (CM_BLK * 2) + (q & 1);
+        long long vc = tcnt[s], vs = tsum[s], vmn = tmin[s], vmx = tmax[s];
+        uint64_t slot = find_slot(nkeys, mask, k[q]);
+        if (slot == ~0ULL) {
+          atomicOr(error_flag, 1);
+        } else {
+          ncnt[slot] = vc;
+          nsum[slot] = vs;
+          nmin[slot] = vmn;
+          nmax[slot] = vmx;
+        }
+      }
+    }
+    const int cnt = __popc(takem);
+    int incl = cnt;
+    for (int off = 1; off < WAVE; off <<= 1) {
+      int o = __shfl_up(incl, off);
+      if (lane >= off) incl += o;
+    }
+    if (lane == WAVE - 1) s_wave[par][wave] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int total = 0;
+      for (int w = 0; w < NW; ++w) total += s_wave[par][w];
+      s_base[par] = total > 0 ? atomicAdd(out_n, total) : 0;
+    }
+    __syncthreads();
+    if (takem != 0) {
+      int64_t idx = (int64_t)s_base[par] + (incl - cnt);
+      for (int w = 0; w < wave; ++w) idx += s_wave[par][w];
+      for (int q = 0; q < CM_PER; ++q) {
+        if (!((takem >> q) & 1u)) continue;
+        if (idx < cap) {
+          int64_t s = s0 + (int64_t)(q >> 1) * (CM_BLK * 2) + (q & 1);
+          out_keys[idx] = (int32_t)(uint32_t)(k[q] & 0xFFFFFFFFULL);
+          out_wins[idx] = (int32_t)(uint32_t)(k[q] >> 32);
+          out_cnt[idx] = tcnt[s];
+          out_sum[idx] = tsum[s];
+          out_min[idx] = tmin[s];
+          out_max[idx] = tmax[s];
+        }
+        ++idx;
+      }
+    }
+  }
+}
+
 // Per-key global join-cell update, "last" insert / "complete" emit
 // semantics (reference operators/__init__.py _JoinLogic): store this
 // side's value; the update that makes all sides present emits the
@@ -5008,6 +5143,75 @@ void stats_extract(
       out_keys.numel());
 }
 
+// Stats close with reclamation (see k_stats_close_migrate); the launch
+// shape of launch_close_migrate.
+void stats_close_migrate(
+    torch::Tensor tkeys,
+    torch::Tensor tcnt,
+    torch::Tensor tsum,
+    torch::Tensor tmin,
+    torch::Tensor tmax,
+    torch::Tensor nkeys,
+    torch::Tensor ncnt,
+    torch::Tensor nsum,
+    torch::Tensor nmin,
+    torch::Tensor nmax,
+    int64_t win_lo,
+    int64_t win_hi,
+    torch::Tensor out_keys,
+    torch::Tensor out_wins,
+    torch::Tensor out_cnt,
+    torch::Tensor out_sum,
+    torch::Tensor out_min,
+    torch::Tensor out_max,
+    torch::Tensor out_n,
+    torch::Tensor error_flag) {
+  check_dev(tkeys, torch::kInt64, "tkeys");
+  check_dev(nkeys, torch::kInt64, "nkeys");
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK(nslots > 0 && (nslots & (nslots - 1)) == 0,
+              "table size must be a power of two");
+  TORCH_CHECK(nkeys.numel() == nslots, "table size mismatch");
+  const torch::Tensor* vals[] = {&tcnt, &tsum, &tmin, &tmax,
+                                 &ncnt, &nsum, &nmin, &nmax};
+  for (const torch::Tensor* t : vals) {
+    check_dev(*t, torch::kInt64, "stats value array");
+    TORCH_CHECK(t->numel() == nslots, "table size mismatch");
+  }
+  check_dev(out_keys, torch::kInt32, "out_keys");
+  check_dev(out_wins, torch::kInt32, "out_wins");
+  check_dev(out_n, torch::kInt32, "out_n");
+  check_dev(error_flag, torch::kInt32, "error_flag");
+  TORCH_CHECK(out_n.numel() >= 1 && error_flag.numel() >= 1,
+              "out_n and error_flag must hold one element");
+  int64_t cap = out_keys.numel();
+  TORCH_CHECK(out_wins.numel() == cap, "output size mismatch");
+  const torch::Tensor* outs[] = {&out_cnt, &out_sum, &out_min, &out_max};
+  for (const torch::Tensor* t : outs) {
+    check_dev(*t, torch::kInt64, "stats output column");
+    TORCH_CHECK(t->numel() == cap, "output size mismatch");
+  }
+  int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  unsigned grid = (unsigned)(nchunks < CM_MAX_GRID ? nchunks : CM_MAX_GRID);
+  hipLaunchKernelGGL(
+      k_stats_close_migrate, dim3(grid), dim3(CM_BLK), 0,
+      at::hip::getCurrentHIPStream(),
+      (const uint64_t*)tkeys.data_ptr<int64_t>(),
+      (const long long*)tcnt.data_ptr<int64_t>(),
+      (const long long*)tsum.data_ptr<int64_t>(),
+      (const long long*)tmin.data_ptr<int64_t>(),
+      (const long long*)tmax.data_ptr<int64_t>(), nslots, win_lo, win_hi,
+      (uint64_t*)nkeys.data_ptr<int64_t>(),
+      (long long*)ncnt.data_ptr<int64_t>(),
+      (long long*)nsum.data_ptr<int64_t>(),
+      (long long*)nmin.data_ptr<int64_t>(),
+      (long long*)nmax.data_ptr<int64_t>(), (uint64_t)(nslots - 1),
+      out_keys.data_ptr<int32_t>(), out_wins.data_ptr<int32_t>(),
+      out_cnt.data_ptr<int64_t>(), out_sum.data_ptr<int64_t>(),
+      out_min.data_ptr<int64_t>(), out_max.data_ptr<int64_t>(),
+      out_n.data_ptr<int32_t>(), cap, error_flag.data_ptr<int32_t>());
+}
+
 void join_insert(
     torch::Tensor keys,
     torch::Tensor vals,
@@ -6679,6 +6883,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Add count/sum deltas to existing stats slots (recovery)");
   m.def("stats_extract", &stats_extract,
         "Extract (and clear) keyed stats below a window horizon");
+  m.def("stats_close_migrate", &stats_close_migrate,
+        "Stats close with reclamation: emit due cells, migrate live "
+        "cells into a fresh table, drop cells below the closed horizon");
   m.def("radix_join_insert", &radix_join_insert,
         "Region-partitioned stream join insert (L2-local table ops)");
   m.def("join_insert", &join_insert,

@@ -919,8 +919,8 @@ class _DeviceStatsLogic(StatefulBatchLogic):
         wm = self.state.watermark_ms() if hasattr(self.state, "watermark_ms") else self.state.max_ts_host
         horizon = (wm - self.wait_ms - self.state.align_ms) // self.state.len_ms
         if horizon > self.state.closed_horizon:
-            closed = self.state.extract(horizon, clear=True)
-            self.state.closed_horizon = horizon
+            # Reclaiming close: the table keeps only the open windows.
+            closed = self.state.close_below(horizon)
             if closed is not None:
                 out.append(closed)
         return (out, StatefulBatchLogic.RETAIN)
@@ -959,6 +959,11 @@ def keyed_stats_agg(
     Use a very long `length` for an unwindowed whole-stream
     aggregation.  Emits dicts of columnar device tensors
     {keys, wins, cnt, sum, min, max} at window close / EOF.
+
+    A window close reclaims the closed cells, so the stream may run
+    unbounded: size `slots_pow` (2^slots_pow table slots, best kept
+    under half full) for the (key, window) cells of the windows that
+    are open at one time, not for every cell the stream will produce.
 
     Ingestion must be watermark-ordered across batches (each batch's
     events at or after the watermark set by the earlier ones, minus

@@ -64,6 +64,11 @@ class StatsAggState:
         self.len_ms = len_ms
         self.max_ts_host = 0
         self.closed_horizon = -(1 << 62)
+        #: The second table (keys, cnt, sum, min, max) that a
+        #: reclaiming close rebuilds the live cells into.  None until
+        #: a close has rows to emit: a whole-stream state never pays
+        #: for it.
+        self.tables_alt: Optional[Tuple[Any, ...]] = None
         self.cpu = device.type == "cpu"
         if self.cpu:
             self._table: Dict[Tuple[int, int], Tuple[int, int, int, int]] = {}
@@ -269,10 +274,13 @@ class StatsAggState:
         (up to +inf if None).  On device the table is never mutated —
         already-emitted cells are excluded by the horizon range (no
         in-place deletion: it would corrupt probe chains); callers
-        advance `closed_horizon` after a closing extract.  Size
-        `slots_pow` for the stream's total distinct (key, window)
-        cells (1BRC-style whole-stream aggregation has exactly one
-        window)."""
+        advance `closed_horizon` after a closing extract.  This call
+        reclaims nothing: a stream that closes windows through it
+        alone needs `slots_pow` sized for its total distinct
+        (key, window) cells (1BRC-style whole-stream aggregation has
+        exactly one window).  Close through :meth:`close_due` /
+        :meth:`close_below` instead and `slots_pow` only has to hold
+        the live working set: the cells of the windows still open."""
         import torch
 
         if horizon is None:
@@ -331,6 +339,120 @@ class StatsAggState:
             "min": self.out["min"][:n].clone(),
             "max": self.out["max"][:n].clone(),
         }
+
+    def close_due(
+        self, wait_ms: Optional[int] = None
+    ) -> Optional[Dict[str, Any]]:
+        """Emit every window fully below the watermark (`max_ts_host`
+        minus `wait_ms`, the constructor's by default) and reclaim its
+        space; None when the horizon has not advanced.  See
+        :meth:`close_below`."""
+        if wait_ms is None:
+            wait_ms = self.wait_ms
+        horizon = (
+            self.max_ts_host - wait_ms - self.align_ms
+        ) // self.len_ms
+        return self.close_below(horizon)
+
+    def close_below(self, horizon: int) -> Optional[Dict[str, Any]]:
+        """Close with reclamation: return the cells of windows in
+        [closed_horizon, horizon) as :meth:`extract` does, keep the
+        cells at or above `horizon`, forget everything below it and
+        advance `closed_horizon` to `horizon`.
+
+        On device the live cells are rebuilt in a second table (see
+        k_stats_close_migrate), the tables are swapped and the retired
+        one is reset on the stream, so the table only ever holds the
+        open windows.  The second table is allocated by the first
+        close that has rows to emit.  A cell below `closed_horizon`
+        (an event behind the watermark that no late tracking caught)
+        was never going to be emitted; it is dropped here."""
+        import torch
+
+        if horizon <= self.closed_horizon:
+            return None
+        win_lo = self.closed_horizon
+        if win_lo < -(1 << 39):
+            win_lo = -(1 << 39)
+        if self.cpu:
+            hit = [
+                (k, w, v)
+                for (k, w), v in self._table.items()
+                if win_lo <= w < horizon
+            ]
+            for kw in [kw for kw in self._table if kw[1] < horizon]:
+                del self._table[kw]
+            self.closed_horizon = horizon
+            if not hit:
+                return None
+            return {
+                "keys": torch.tensor([k for k, _w, _v in hit], dtype=torch.int32),
+                "wins": torch.tensor([w for _k, w, _v in hit], dtype=torch.int32),
+                "cnt": torch.tensor([v[0] for *_x, v in hit], dtype=torch.int64),
+                "sum": torch.tensor([v[1] for *_x, v in hit], dtype=torch.int64),
+                "min": torch.tensor([v[2] for *_x, v in hit], dtype=torch.int64),
+                "max": torch.tensor([v[3] for *_x, v in hit], dtype=torch.int64),
+            }
+        if self.tables_alt is None:
+            # Until something is due there is nothing to reclaim: a
+            # whole-stream state, whose operator asks once for the
+            # windows below its only one, never pays for the second
+            # table.  The stream's first close with rows scans twice.
+            if self.extract(horizon, clear=False) is None:
+                self.closed_horizon = horizon
+                return None
+            self.tables_alt = tuple(
+                torch.full(
+                    (self.nslots,), fill, dtype=torch.int64, device=self.device
+                )
+                for fill in (-1, 0, 0, _I64_MAX, _I64_MIN)
+            )
+        live = (self.tkeys, self.tcnt, self.tsum, self.tmin, self.tmax)
+        self.out_n.zero_()
+        self.k.stats_close_migrate(
+            *live,
+            *self.tables_alt,
+            win_lo,
+            min(horizon, 1 << 40),
+            self.out_keys,
+            self.out_wins,
+            self.out["cnt"],
+            self.out["sum"],
+            self.out["min"],
+            self.out["max"],
+            self.out_n,
+            self.error_flag,
+        )
+        (
+            self.tkeys, self.tcnt, self.tsum, self.tmin, self.tmax
+        ) = self.tables_alt
+        self.tables_alt = live
+        # Reset the retired table asynchronously for the next close.
+        for t, fill in zip(live, (-1, 0, 0, _I64_MAX, _I64_MIN)):
+            t.fill_(fill)
+        n = int(self.out_n.item())
+        if n > self.out_cap:
+            msg = f"stats extract produced {n} rows > out_cap"
+            raise RuntimeError(msg)
+        _check_error_flag(int(self.error_flag.item()), "stats table")
+        self.closed_horizon = horizon
+        if n == 0:
+            return None
+        return {
+            "keys": self.out_keys[:n].clone(),
+            "wins": self.out_wins[:n].clone(),
+            "cnt": self.out["cnt"][:n].clone(),
+            "sum": self.out["sum"][:n].clone(),
+            "min": self.out["min"][:n].clone(),
+            "max": self.out["max"][:n].clone(),
+        }
+
+    def close_all(self) -> Optional[Dict[str, Any]]:
+        """EOF: every cell at or above the closed horizon, read without
+        mutating the device table."""
+        out = self.extract(None, clear=True)
+        self.closed_horizon = 1 << 40
+        return out
 
     def snapshot_to_host(self) -> Dict[str, Any]:
         import torch

@@ -1058,9 +1058,13 @@ class _ColumnarWindowLogic(StatefulBatchLogic):
 
         if horizon is not None and horizon <= self.state.closed_horizon:
             return None
-        cols = self.state.extract(horizon, clear=True)
-        if horizon is not None:
-            self.state.closed_horizon = horizon
+        if horizon is None:
+            # EOF: nothing is inserted afterwards, so read in place.
+            cols = self.state.extract(None, clear=True)
+        else:
+            # Watermark close: emit the due cells and reclaim them, so
+            # the table holds only the open windows of the stream.
+            cols = self.state.close_below(horizon)
         if cols is None:
             return None
         wins = cols["wins"].to(dtype=cols["cnt"].dtype)
