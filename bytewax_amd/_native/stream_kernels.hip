@@ -2446,6 +2446,136 @@ __global__ __launch_bounds__(CM_BLK) void k_stats_close_migrate(
   }
 }
 
+__device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {
+  int64_t q = a / b;
+  return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
+}
+
+// Sliding stats close: fold panes into windows and reclaim dead panes
+// in one pass over the pane table.  The table holds one cell per
+// (key, pane), a pane being gcd(length, offset) wide; window `w` is
+// the `L` panes [w * o, w * o + L), so pane `p` lies in the windows
+// floor((p - L) / o) + 1 .. floor(p / o).  Every occupied cell
+//   - is folded into each of its windows in [win_lo, win_hi): the
+//     cell (key, w) is claimed in the separate fold table and the
+//     pane's count/sum/min/max are merged into it with atomicAdd,
+//     atomicAdd, atomicMin, atomicMax (count and sum add, min and max
+//     observe, so the merge of the panes equals the aggregate of the
+//     window's events in any order);
+//   - is copied into the fresh table when p >= pane_keep (some window
+//     that contains it is still open), exactly as
+//     k_stats_close_migrate migrates, and dropped otherwise.
+// A pane next to the horizon is both folded and migrated.  The kernel
+// emits no rows: the caller runs k_stats_extract over the fold table,
+// subtracts L from the window column and refills the fold table's
+// five arrays.
+//
+// The chunked shape is k_stats_close_migrate's: 16-byte key loads,
+// CM_CHUNK slots per block step, values read only for a cell that is
+// folded or migrated.  No row reservation, so no LDS and no barrier.
+//
+// Window ids below zero are normal here (the first L - 1 panes after
+// `align` lie in windows that open before it), and (w = -1, key = -1)
+// would pack to EMPTY_SLOT, so the fold table stores w + L in the
+// high half.  With t >= align every pane id is >= 0, every window id
+// >= 1 - L and the stored value >= 1; a window below 1 - L (an event
+// before `align`, which the stats kernels do not support) is skipped.
+//
+// Exactness.  Migration: as k_stats_close_migrate, (1) the target is
+// fresh and each migrated cell unique, (2) every other writer of
+// either table runs on the same stream.  Fold table: (1) it is all
+// EMPTY / 0 / 0 / I64_MAX / I64_MIN when the kernel starts, because
+// the fills that follow the previous extract are on the same stream;
+// (2) `find_slot` hands every thread that folds into (key, w) the
+// same slot, and the four merges into it are atomics that commute, so
+// the up to L threads that meet there need no order; the fills are
+// the identities of the four merges, so a slot needs no first-writer
+// initialisation; (3) nothing reads the fold table before the kernel
+// has finished: the extract is the next launch on the stream, and
+// nothing else ever writes it.
+__global__ __launch_bounds__(CM_BLK) void k_stats_pane_close(
+    const uint64_t* __restrict__ tkeys,
+    const long long* __restrict__ tcnt,
+    const long long* __restrict__ tsum,
+    const long long* __restrict__ tmin,
+    const long long* __restrict__ tmax,
+    int64_t nslots,
+    int64_t win_lo,
+    int64_t win_hi,
+    int64_t pane_keep,
+    int64_t L,
+    int64_t o,
+    uint64_t* __restrict__ nkeys,
+    long long* __restrict__ ncnt,
+    long long* __restrict__ nsum,
+    long long* __restrict__ nmin,
+    long long* __restrict__ nmax,
+    uint64_t mask,
+    uint64_t* __restrict__ fkeys,
+    long long* __restrict__ fcnt,
+    long long* __restrict__ fsum,
+    long long* __restrict__ fmin,
+    long long* __restrict__ fmax,
+    uint64_t fmask,
+    int* __restrict__ error_flag) {
+  const bool vec = (((uintptr_t)tkeys) & 15) == 0;
+  const int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    // Slot of k[q]: s0 + (q / 2) * (CM_BLK * 2) + (q & 1).
+    const int64_t s0 = c * CM_CHUNK + threadIdx.x * 2;
+    uint64_t k[CM_PER];
+    for (int j = 0; j < CM_PER / 2; ++j) {
+      int64_t s = s0 + (int64_t)j * (CM_BLK * 2);
+      if (vec && s + 1 < nslots) {
+        ulonglong2 kk = *(const ulonglong2*)(tkeys + s);
+        k[2 * j] = kk.x;
+        k[2 * j + 1] = kk.y;
+      } else {
+        for (int q = 0; q < 2; ++q) {
+          k[2 * j + q] = s + q < nslots ? tkeys[s + q] : EMPTY_SLOT;
+        }
+      }
+    }
+    for (int q = 0; q < CM_PER; ++q) {
+      if (k[q] == EMPTY_SLOT) continue;
+      int64_t p = (int64_t)(int32_t)(uint32_t)(k[q] >> 32);
+      int64_t lo = floor_div(p - L, o) + 1;
+      int64_t hi = floor_div(p, o);
+      if (lo < win_lo) lo = win_lo;
+      if (lo < 1 - L) lo = 1 - L;
+      if (hi > win_hi - 1) hi = win_hi - 1;
+      const bool keep = p >= pane_keep;
+      if (lo > hi && !keep) continue;
+      int64_t s = s0 + (int64_t)(q >> 1) * (CM_BLK * 2) + (q & 1);
+      long long vc = tcnt[s], vs = tsum[s], vmn = tmin[s], vmx = tmax[s];
+      const uint64_t key = k[q] & 0xFFFFFFFFULL;
+      for (int64_t w = lo; w <= hi; ++w) {
+        uint64_t packed = ((uint64_t)(uint32_t)(int32_t)(w + L) << 32) | key;
+        uint64_t slot = find_slot(fkeys, fmask, packed);
+        if (slot == ~0ULL) {
+          atomicOr(error_flag, 1);
+          break;
+        }
+        atomicAdd((unsigned long long*)&fcnt[slot], (unsigned long long)vc);
+        atomicAdd((unsigned long long*)&fsum[slot], (unsigned long long)vs);
+        atomicMin(&fmin[slot], vmn);
+        atomicMax(&fmax[slot], vmx);
+      }
+      if (keep) {
+        uint64_t slot = find_slot(nkeys, mask, k[q]);
+        if (slot == ~0ULL) {
+          atomicOr(error_flag, 1);
+        } else {
+          ncnt[slot] = vc;
+          nsum[slot] = vs;
+          nmin[slot] = vmn;
+          nmax[slot] = vmx;
+        }
+      }
+    }
+  }
+}
+
 // Per-key global join-cell update, "last" insert / "complete" emit
 // semantics (reference operators/__init__.py _JoinLogic): store this
 // side's value; the update that makes all sides present emits the
@@ -5212,6 +5342,86 @@ void stats_close_migrate(
       out_n.data_ptr<int32_t>(), cap, error_flag.data_ptr<int32_t>());
 }
 
+// Sliding stats close (see k_stats_pane_close): folds the panes of the
+// windows in [win_lo, win_hi) into the fold table `f*` and migrates
+// the panes at or above `pane_keep` into the fresh table `n*`.  The
+// launch shape of stats_close_migrate.
+void stats_pane_close(
+    torch::Tensor tkeys,
+    torch::Tensor tcnt,
+    torch::Tensor tsum,
+    torch::Tensor tmin,
+    torch::Tensor tmax,
+    torch::Tensor nkeys,
+    torch::Tensor ncnt,
+    torch::Tensor nsum,
+    torch::Tensor nmin,
+    torch::Tensor nmax,
+    torch::Tensor fkeys,
+    torch::Tensor fcnt,
+    torch::Tensor fsum,
+    torch::Tensor fmin,
+    torch::Tensor fmax,
+    int64_t win_lo,
+    int64_t win_hi,
+    int64_t pane_keep,
+    int64_t panes_per_window,
+    int64_t panes_per_offset,
+    torch::Tensor error_flag) {
+  check_dev(tkeys, torch::kInt64, "tkeys");
+  check_dev(nkeys, torch::kInt64, "nkeys");
+  check_dev(fkeys, torch::kInt64, "fkeys");
+  int64_t nslots = tkeys.numel();
+  int64_t fslots = fkeys.numel();
+  TORCH_CHECK(nslots > 0 && (nslots & (nslots - 1)) == 0,
+              "table size must be a power of two");
+  TORCH_CHECK(fslots > 0 && (fslots & (fslots - 1)) == 0,
+              "fold table size must be a power of two");
+  TORCH_CHECK(nkeys.numel() == nslots, "table size mismatch");
+  TORCH_CHECK(nkeys.data_ptr() != tkeys.data_ptr() &&
+                  fkeys.data_ptr() != tkeys.data_ptr() &&
+                  fkeys.data_ptr() != nkeys.data_ptr(),
+              "the three tables must be distinct");
+  const torch::Tensor* vals[] = {&tcnt, &tsum, &tmin, &tmax,
+                                 &ncnt, &nsum, &nmin, &nmax};
+  for (const torch::Tensor* t : vals) {
+    check_dev(*t, torch::kInt64, "stats value array");
+    TORCH_CHECK(t->numel() == nslots, "table size mismatch");
+  }
+  const torch::Tensor* fvals[] = {&fcnt, &fsum, &fmin, &fmax};
+  for (const torch::Tensor* t : fvals) {
+    check_dev(*t, torch::kInt64, "fold value array");
+    TORCH_CHECK(t->numel() == fslots, "fold table size mismatch");
+  }
+  check_dev(error_flag, torch::kInt32, "error_flag");
+  TORCH_CHECK(error_flag.numel() >= 1, "error_flag must hold one element");
+  TORCH_CHECK(panes_per_offset >= 1 && panes_per_window >= panes_per_offset &&
+                  panes_per_window <= 64,
+              "need 1 <= panes per offset <= panes per window <= 64");
+  int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  unsigned grid = (unsigned)(nchunks < CM_MAX_GRID ? nchunks : CM_MAX_GRID);
+  hipLaunchKernelGGL(
+      k_stats_pane_close, dim3(grid), dim3(CM_BLK), 0,
+      at::hip::getCurrentHIPStream(),
+      (const uint64_t*)tkeys.data_ptr<int64_t>(),
+      (const long long*)tcnt.data_ptr<int64_t>(),
+      (const long long*)tsum.data_ptr<int64_t>(),
+      (const long long*)tmin.data_ptr<int64_t>(),
+      (const long long*)tmax.data_ptr<int64_t>(), nslots, win_lo, win_hi,
+      pane_keep, panes_per_window, panes_per_offset,
+      (uint64_t*)nkeys.data_ptr<int64_t>(),
+      (long long*)ncnt.data_ptr<int64_t>(),
+      (long long*)nsum.data_ptr<int64_t>(),
+      (long long*)nmin.data_ptr<int64_t>(),
+      (long long*)nmax.data_ptr<int64_t>(), (uint64_t)(nslots - 1),
+      (uint64_t*)fkeys.data_ptr<int64_t>(),
+      (long long*)fcnt.data_ptr<int64_t>(),
+      (long long*)fsum.data_ptr<int64_t>(),
+      (long long*)fmin.data_ptr<int64_t>(),
+      (long long*)fmax.data_ptr<int64_t>(), (uint64_t)(fslots - 1),
+      error_flag.data_ptr<int32_t>());
+}
+
 void join_insert(
     torch::Tensor keys,
     torch::Tensor vals,
@@ -6886,6 +7096,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stats_close_migrate", &stats_close_migrate,
         "Stats close with reclamation: emit due cells, migrate live "
         "cells into a fresh table, drop cells below the closed horizon");
+  m.def("stats_pane_close", &stats_pane_close,
+        "Sliding stats close: fold the panes of due windows into a fold "
+        "table, migrate live panes into a fresh table, drop dead panes");
   m.def("radix_join_insert", &radix_join_insert,
         "Region-partitioned stream join insert (L2-local table ops)");
   m.def("join_insert", &join_insert,

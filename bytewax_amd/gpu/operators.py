@@ -830,6 +830,10 @@ class _DeviceStatsLogic(StatefulBatchLogic):
         self._world = world
         self._registry = registry
         self._applied_rescale = registry is None
+        # Rows a rescale merge had to close (see
+        # `SlidingStatsAggState.merge_donors`); emitted by the
+        # activation that applied it.
+        self._rescale_out: List[Dict[str, Any]] = []
         if resume is not None:
             resume = dict(resume)
             resume.pop("__world__", None)
@@ -853,28 +857,23 @@ class _DeviceStatsLogic(StatefulBatchLogic):
 
         from . import key_owner
 
-        rows = []
+        # One part per donor shard: its rows and what the state needs
+        # to travel with them (the window horizon of a sliding state).
+        local = []
         max_ts = None
         for entry in self._registry.rescale_rows:
             if entry["consumed"]:
                 continue
             entry["consumed"] = True
             snap = entry["snap"]
+            meta = self.state.donor_meta(snap)
             if len(snap.get("keys", ())):
-                rows.append(
-                    {c: np.asarray(snap[c]) for c in _STATS_COLS}
-                )
+                part = {c: np.asarray(snap[c]) for c in _STATS_COLS}
+                part["meta"] = meta
+                local.append(part)
             mts = snap.get("max_ts")
             if mts is not None:
                 max_ts = mts if max_ts is None else max(max_ts, mts)
-        local = (
-            {
-                c: np.concatenate([r[c] for r in rows])
-                for c in _STATS_COLS
-            }
-            if rows
-            else None
-        )
         if self.exchange:
             import torch.distributed as dist
 
@@ -884,25 +883,17 @@ class _DeviceStatsLogic(StatefulBatchLogic):
             dist.all_gather_object(gathered, local)
             parts = []
             for g in gathered:
-                if g is None:
-                    continue
-                # Same owner as the exchange kernels give live events.
-                keys_t = torch.as_tensor(g["keys"]).to(torch.int32)
-                mine = (key_owner(keys_t, world) == rank).numpy()
-                if mine.any():
-                    parts.append({c: g[c][mine] for c in _STATS_COLS})
-            merged = (
-                {
-                    c: np.concatenate([p[c] for p in parts])
-                    for c in _STATS_COLS
-                }
-                if parts
-                else None
-            )
+                for part in g:
+                    # Same owner as the exchange kernels give live events.
+                    keys_t = torch.as_tensor(part["keys"]).to(torch.int32)
+                    mine = (key_owner(keys_t, world) == rank).numpy()
+                    if mine.any():
+                        kept = {c: part[c][mine] for c in _STATS_COLS}
+                        kept["meta"] = part["meta"]
+                        parts.append(kept)
         else:
-            merged = local
-        if merged is not None:
-            self.state.merge_rows(merged)
+            parts = local
+        self._rescale_out = self.state.merge_donors(parts)
         if (
             max_ts is not None
             and max_ts > self.state.max_ts_host
@@ -911,27 +902,29 @@ class _DeviceStatsLogic(StatefulBatchLogic):
 
     def on_batch(self, batches):
         self._apply_rescale()
-        out = []
+        out, self._rescale_out = self._rescale_out, []
         for batch in batches:
             if self.exchange:
                 batch = exchange_by_key(batch)
             self.state.insert(batch)
         wm = self.state.watermark_ms() if hasattr(self.state, "watermark_ms") else self.state.max_ts_host
-        horizon = (wm - self.wait_ms - self.state.align_ms) // self.state.len_ms
-        if horizon > self.state.closed_horizon:
-            # Reclaiming close: the table keeps only the open windows.
-            closed = self.state.close_below(horizon)
-            if closed is not None:
-                out.append(closed)
+        # Reclaiming close: the table keeps only the open windows (the
+        # panes of the open windows, for a sliding state).  None when
+        # the horizon has not advanced.
+        closed = self.state.close_below(
+            self.state.horizon_for(wm, self.wait_ms)
+        )
+        if closed is not None:
+            out.append(closed)
         return (out, StatefulBatchLogic.RETAIN)
 
     def on_eof(self):
         self._apply_rescale()
-        closed = self.state.extract(None, clear=True)
-        return (
-            [closed] if closed is not None else [],
-            StatefulBatchLogic.RETAIN,
-        )
+        out, self._rescale_out = self._rescale_out, []
+        closed = self.state.close_eof()
+        if closed is not None:
+            out.append(closed)
+        return (out, StatefulBatchLogic.RETAIN)
 
     def snapshot(self):
         snap = dict(self.state.snapshot_to_host())
@@ -952,6 +945,7 @@ def keyed_stats_agg(
     out_cap: int = 1 << 20,
     device: str = "cuda",
     exchange: Optional[bool] = None,
+    offset: Optional[timedelta] = None,
 ) -> Stream[Dict[str, Any]]:
     """Keyed windowed count/sum/min/max (1BRC-style) over columnar
     batches on GPU; one fused pass per batch.
@@ -959,6 +953,21 @@ def keyed_stats_agg(
     Use a very long `length` for an unwindowed whole-stream
     aggregation.  Emits dicts of columnar device tensors
     {keys, wins, cnt, sum, min, max} at window close / EOF.
+
+    With `offset` shorter than `length` the windows slide: one opens
+    every `offset` and each lasts `length`, as `SlidingWindower`'s do.
+    `wins` counts `offset` strides, so a row's window starts at
+    ``align_to + wins * offset`` (with no `offset`, or ``offset ==
+    length``, that is the tumbling ``align_to + wins * length``) and
+    ends `length` later; ids below zero are windows that opened before
+    `align_to`.  Events are aggregated once into panes of
+    ``gcd(length, offset)`` and a close folds the panes of each due
+    window (see `SlidingStatsAggState`), so an insert costs what a
+    tumbling window of that pane width costs.  Limits: at most 64
+    panes per window (``length / gcd(length, offset) <= 64``), no
+    event before `align_to`, and ``(t - align_to) / gcd`` within
+    int32.  Size `slots_pow` for the live panes: keys times (panes
+    per window plus the panes the watermark lags by).
 
     A window close reclaims the closed cells, so the stream may run
     unbounded: size `slots_pow` (2^slots_pow table slots, best kept
@@ -979,12 +988,15 @@ def keyed_stats_agg(
 
     import torch
 
-    from .state import StatsAggState
+    from .state import SlidingStatsAggState, StatsAggState
     from . import _ms as to_ms
 
     align_ms = to_ms(align_to)
     len_ms = int(length.total_seconds() * 1000)
     wait_ms = int(wait.total_seconds() * 1000)
+    off_ms = None if offset is None else int(offset.total_seconds() * 1000)
+    if off_ms == len_ms:
+        off_ms = None
 
     _rt = threading.local()
 
@@ -1018,10 +1030,16 @@ def keyed_stats_agg(
                 resume_state = None
             elif snap_shard != rt.shard:
                 return _DonorLogic(resume_state, rt)
-        state = StatsAggState(
-            torch.device(device), align_ms, len_ms,
-            slots_pow=slots_pow, out_cap=out_cap,
-        )
+        if off_ms is None:
+            state = StatsAggState(
+                torch.device(device), align_ms, len_ms,
+                slots_pow=slots_pow, out_cap=out_cap,
+            )
+        else:
+            state = SlidingStatsAggState(
+                torch.device(device), align_ms, len_ms, off_ms,
+                slots_pow=slots_pow, out_cap=out_cap,
+            )
         return _DeviceStatsLogic(
             state,
             wait_ms,

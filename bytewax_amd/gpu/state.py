@@ -20,6 +20,7 @@ from ._ext import ext
 
 _I64_MAX = (1 << 63) - 1
 _I64_MIN = -(1 << 63)
+_STATS_COLS = ("keys", "wins", "cnt", "sum", "min", "max")
 
 
 def _wrap64(x: int) -> int:
@@ -347,12 +348,22 @@ class StatsAggState:
         minus `wait_ms`, the constructor's by default) and reclaim its
         space; None when the horizon has not advanced.  See
         :meth:`close_below`."""
+        return self.close_below(self.horizon_for(self.max_ts_host, wait_ms))
+
+    def horizon_for(
+        self, watermark_ms: int, wait_ms: Optional[int] = None
+    ) -> int:
+        """The window horizon of a watermark: every window below it
+        ends at or before `watermark_ms` minus `wait_ms` (the
+        constructor's by default).  What :meth:`close_below` takes."""
         if wait_ms is None:
             wait_ms = self.wait_ms
-        horizon = (
-            self.max_ts_host - wait_ms - self.align_ms
-        ) // self.len_ms
-        return self.close_below(horizon)
+        return (watermark_ms - wait_ms - self.align_ms) // self.len_ms
+
+    def close_eof(self) -> Optional[Dict[str, Any]]:
+        """End of input, as the operator closes it: every cell at or
+        above the closed horizon, with the horizon left where it is."""
+        return self.extract(None, clear=True)
 
     def close_below(self, horizon: int) -> Optional[Dict[str, Any]]:
         """Close with reclamation: return the cells of windows in
@@ -470,12 +481,48 @@ class StatsAggState:
         out["n"] = len(out["keys"])
         return out
 
+    def _check_geometry(self, snap: Dict[str, Any]) -> None:
+        """Refuse a snapshot of another window shape: a sliding
+        state's rows are panes, not windows."""
+        if "win_len_ms" in snap or "off_ms" in snap:
+            msg = (
+                "snapshot of sliding stats windows (length, offset) = "
+                f"{(snap.get('win_len_ms'), snap.get('off_ms'))} ms cannot "
+                "restore a tumbling stats state"
+            )
+            raise ValueError(msg)
+
     def restore_from_host(self, snap: Dict[str, Any]) -> None:
+        self._check_geometry(snap)
         self.max_ts_host = snap["max_ts"]
         self.closed_horizon = snap["closed_horizon"]
         if snap["n"] == 0:
             return
         self.merge_rows(snap)
+
+    def donor_meta(self, snap: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+        """Rescale: what of a donor shard's snapshot has to travel
+        with its rows (checked against this state's window shape).
+        Nothing for tumbling windows: no cell of an emitted window is
+        ever kept."""
+        self._check_geometry(snap)
+        return None
+
+    def merge_donors(self, parts) -> List[Dict[str, Any]]:
+        """Rescale: merge the rows of donor shards, each a dict of the
+        six columns plus ``"meta"`` from :meth:`donor_meta`.  Returns
+        rows that have to be emitted at once (none here)."""
+        import numpy as np
+
+        parts = [p for p in parts if len(p["keys"])]
+        if parts:
+            self.merge_rows(
+                {
+                    c: np.concatenate([np.asarray(p[c]) for p in parts])
+                    for c in _STATS_COLS
+                }
+            )
+        return []
 
     def merge_rows(self, snap: Dict[str, Any]) -> None:
         """Additively merge saved stats rows into the live table
@@ -543,6 +590,366 @@ class StatsAggState:
         self.k.stats_fixup(
             keys, ts, cnt_fix, sum_fix, self.tkeys, self.tcnt, self.tsum,
             self.align_ms, self.len_ms,
+        )
+
+
+_STATS_FILLS = (-1, 0, 0, _I64_MAX, _I64_MIN)
+
+
+def _stats_rows(hit) -> Dict[str, Any]:
+    """The six-column dict of a list of (key, win, (cnt, sum, min, max))."""
+    import torch
+
+    return {
+        "keys": torch.tensor([k for k, _w, _v in hit], dtype=torch.int32),
+        "wins": torch.tensor([w for _k, w, _v in hit], dtype=torch.int32),
+        "cnt": torch.tensor([v[0] for *_x, v in hit], dtype=torch.int64),
+        "sum": torch.tensor([v[1] for *_x, v in hit], dtype=torch.int64),
+        "min": torch.tensor([v[2] for *_x, v in hit], dtype=torch.int64),
+        "max": torch.tensor([v[3] for *_x, v in hit], dtype=torch.int64),
+    }
+
+
+class SlidingStatsAggState(StatsAggState):
+    """Keyed count/sum/min/max over sliding windows on device.
+
+    Window `w` spans ``[align + w * off, align + w * off + len)``, the
+    ids of `SlidingWindower`.  Events are aggregated once, by the
+    parent's insert kernels, into non-overlapping *panes* of width
+    ``g = gcd(len_ms, off_ms)``: the table holds (key, pane) cells and
+    an insert costs what a tumbling window of length `g` costs.  A
+    window is the ``L = len_ms / g`` panes ``[w * o, w * o + L)`` with
+    ``o = off_ms / g``; count and sum add and min and max observe, so a
+    close folds the panes of every due window into a separate fold
+    table (k_stats_pane_close), reads the rows out of it and drops the
+    panes that no open window contains.  An event that is not late
+    lies in no closed window, so the result is the host windower's.
+
+    `insert`, `take_late`, `snapshot_to_host`, `restore_from_host`,
+    `merge_rows` and `extract` work on pane cells (the parent's
+    `len_ms` is `g` and its `closed_horizon` the pane floor); the
+    closing calls return windows.
+
+    A pane outlives the windows that have closed over it for as long
+    as an open window contains it, so pane rows alone do not say which
+    windows are still owed: the window horizon travels with them, in
+    snapshots and through a rescale (:meth:`merge_donors`).
+
+    Limits:
+
+    - ``L <= 64``.  The table holds up to `L` live cells per key, so
+      size `slots_pow` for ``keys x (L + panes per watermark lag)``;
+      the cap keeps that growth, and the ``w + L`` the fold table
+      stores, small.
+    - The fold table (`fold_slots_pow`, the table's size by default)
+      has to hold the (key, window) rows of one close, kept under half
+      full.  Reading the rows out and refilling it costs time in
+      proportion to its size, so a stream that closes one window per
+      close does best with a fold table sized for ``2 x keys``.
+    - Event times must not precede `align_ms` (the stats kernels
+      truncate towards zero), and pane ids ``(t - align_ms) / g`` must
+      fit in int32.
+    """
+
+    MAX_PANES = 64
+
+    def __init__(
+        self,
+        device,
+        align_ms: int,
+        len_ms: int,
+        off_ms: int,
+        slots_pow: int = 20,
+        out_cap: int = 1 << 20,
+        radix: bool = True,
+        region_bits: int = 10,
+        track_late: bool = False,
+        wait_ms: int = 0,
+        late_cap: int = 0,
+        fold_slots_pow: Optional[int] = None,
+    ):
+        import math
+
+        if off_ms <= 0:
+            msg = "sliding stats `off_ms` must be positive"
+            raise ValueError(msg)
+        if off_ms > len_ms:
+            msg = (
+                "sliding stats `off_ms` can't be longer than `len_ms`; "
+                "there would be gaps between windows"
+            )
+            raise ValueError(msg)
+        g = math.gcd(len_ms, off_ms)
+        if len_ms // g > self.MAX_PANES:
+            msg = (
+                f"sliding stats window of {len_ms} ms every {off_ms} ms "
+                f"needs {len_ms // g} panes of {g} ms per window; at "
+                f"most {self.MAX_PANES} are supported"
+            )
+            raise ValueError(msg)
+        super().__init__(
+            device, align_ms, g, slots_pow=slots_pow, out_cap=out_cap,
+            radix=radix, region_bits=region_bits, track_late=track_late,
+            wait_ms=wait_ms, late_cap=late_cap,
+        )
+        self.win_len_ms = len_ms
+        self.off_ms = off_ms
+        self.panes_per_window = len_ms // g
+        self.panes_per_offset = off_ms // g
+        #: Windows below this id have been emitted.
+        self.win_horizon = -(1 << 62)
+        #: The fold table (keys, cnt, sum, min, max); None until a
+        #: close has windows to build.
+        self.fold: Optional[Tuple[Any, ...]] = None
+        if not self.cpu:
+            self.fold_slots = (
+                self.nslots if fold_slots_pow is None else 1 << fold_slots_pow
+            )
+
+    def horizon_for(
+        self, watermark_ms: int, wait_ms: Optional[int] = None
+    ) -> int:
+        """Window `w` is due once ``w * off + len`` is at or below the
+        watermark minus `wait_ms`; the windows below the returned id
+        are."""
+        if wait_ms is None:
+            wait_ms = self.wait_ms
+        rel = watermark_ms - wait_ms - self.align_ms
+        return (rel - self.win_len_ms) // self.off_ms + 1
+
+    def close_below(self, horizon: int) -> Optional[Dict[str, Any]]:
+        """Return the windows in [win_horizon, horizon), folded from
+        their panes, forget the panes that lie in no window at or above
+        `horizon`, and advance `win_horizon` to `horizon` and the pane
+        floor `closed_horizon` to ``horizon * o``.
+
+        On device one kernel folds and migrates (k_stats_pane_close);
+        the rows are then extracted from the fold table, which is
+        refilled for the next close, all on the one stream.  The fold
+        table and the second table are allocated by the first close
+        that has a window to build."""
+        if horizon <= self.win_horizon:
+            return None
+        win_hi = min(horizon, 1 << 40)
+        pane_keep = win_hi * self.panes_per_offset
+        out = self._fold(win_hi, pane_keep)
+        self.win_horizon = horizon
+        self.closed_horizon = pane_keep
+        return out
+
+    def _fold(self, win_hi: int, pane_keep: int) -> Optional[Dict[str, Any]]:
+        """The rows of the windows in [win_horizon, win_hi); panes
+        below `pane_keep` are forgotten.  Moves no horizon."""
+        import torch
+
+        n_w, n_o = self.panes_per_window, self.panes_per_offset
+        win_lo = max(self.win_horizon, -(1 << 39))
+        if self.cpu:
+            folded: Dict[Tuple[int, int], Tuple[int, int, int, int]] = {}
+            for (k, p), v in self._table.items():
+                w_first = (p - n_w) // n_o + 1
+                w_last = p // n_o
+                for w in range(max(w_first, win_lo), min(w_last, win_hi - 1) + 1):
+                    cur = folded.get((k, w), (0, 0, _I64_MAX, _I64_MIN))
+                    folded[(k, w)] = (
+                        cur[0] + v[0],
+                        _wrap64(cur[1] + v[1]),
+                        min(cur[2], v[2]),
+                        max(cur[3], v[3]),
+                    )
+            for kp in [kp for kp in self._table if kp[1] < pane_keep]:
+                del self._table[kp]
+            if not folded:
+                return None
+            return _stats_rows([(k, w, v) for (k, w), v in folded.items()])
+        if self.tables_alt is None:
+            # A pane lies in a window below `win_hi` iff it is below
+            # (win_hi - 1) * o + L, and a pane is dropped iff it is
+            # below `pane_keep`: with no pane under the larger of the
+            # two there is nothing to fold or to drop.
+            bound = max((win_hi - 1) * n_o + n_w, pane_keep)
+            if not self._any_pane_below(bound):
+                return None
+            self.tables_alt = tuple(
+                torch.full(
+                    (self.nslots,), fill, dtype=torch.int64, device=self.device
+                )
+                for fill in _STATS_FILLS
+            )
+        if self.fold is None:
+            self.fold = tuple(
+                torch.full(
+                    (self.fold_slots,), fill, dtype=torch.int64,
+                    device=self.device,
+                )
+                for fill in _STATS_FILLS
+            )
+        live = (self.tkeys, self.tcnt, self.tsum, self.tmin, self.tmax)
+        self.k.stats_pane_close(
+            *live,
+            *self.tables_alt,
+            *self.fold,
+            win_lo,
+            win_hi,
+            pane_keep,
+            n_w,
+            n_o,
+            self.error_flag,
+        )
+        (
+            self.tkeys, self.tcnt, self.tsum, self.tmin, self.tmax
+        ) = self.tables_alt
+        self.tables_alt = live
+        for t, fill in zip(live, _STATS_FILLS):
+            t.fill_(fill)
+        # Every occupied fold cell is a row; its window column holds
+        # w + L (see the kernel).
+        self.out_n.zero_()
+        self.k.stats_extract(
+            *self.fold,
+            0,
+            1 << 40,
+            self.out_keys,
+            self.out_wins,
+            self.out["cnt"],
+            self.out["sum"],
+            self.out["min"],
+            self.out["max"],
+            self.out_n,
+        )
+        for t, fill in zip(self.fold, _STATS_FILLS):
+            t.fill_(fill)
+        n = int(self.out_n.item())
+        if n > self.out_cap:
+            msg = f"stats extract produced {n} rows > out_cap"
+            raise RuntimeError(msg)
+        _check_error_flag(int(self.error_flag.item()), "stats table")
+        if n == 0:
+            return None
+        return {
+            "keys": self.out_keys[:n].clone(),
+            "wins": self.out_wins[:n] - n_w,
+            "cnt": self.out["cnt"][:n].clone(),
+            "sum": self.out["sum"][:n].clone(),
+            "min": self.out["min"][:n].clone(),
+            "max": self.out["max"][:n].clone(),
+        }
+
+    def _any_pane_below(self, bound: int) -> bool:
+        """Whether the table holds a pane in [closed_horizon, bound).
+        `k_stats_extract` counts the rows past the buffers' capacity
+        without writing them, so the count alone is read."""
+        self.out_n.zero_()
+        self.k.stats_extract(
+            self.tkeys,
+            self.tcnt,
+            self.tsum,
+            self.tmin,
+            self.tmax,
+            max(self.closed_horizon, -(1 << 39)),
+            bound,
+            self.out_keys,
+            self.out_wins,
+            self.out["cnt"],
+            self.out["sum"],
+            self.out["min"],
+            self.out["max"],
+            self.out_n,
+        )
+        return int(self.out_n.item()) > 0
+
+    def close_all(self) -> Optional[Dict[str, Any]]:
+        """Every window that still holds a pane, the unfinished ones
+        included; :meth:`close_below` with an unbounded horizon.  The
+        state takes no further input afterwards."""
+        return self.close_below(1 << 40)
+
+    def close_eof(self) -> Optional[Dict[str, Any]]:
+        """End of input, as the operator closes it: the rows of every
+        window at or above `win_horizon`, the unfinished ones included,
+        with both horizons and every live pane left where they are, as
+        the tumbling :meth:`StatsAggState.close_eof` leaves its table.
+        A snapshot taken afterwards resumes exactly: an execution that
+        continues the stream emits the windows that were unfinished
+        here again, complete, when they fall due."""
+        return self._fold(1 << 40, self.closed_horizon)
+
+    def snapshot_to_host(self) -> Dict[str, Any]:
+        out = super().snapshot_to_host()
+        out["win_horizon"] = self.win_horizon
+        out["win_len_ms"] = self.win_len_ms
+        out["off_ms"] = self.off_ms
+        return out
+
+    def _check_geometry(self, snap: Dict[str, Any]) -> None:
+        geom = (snap.get("win_len_ms"), snap.get("off_ms"))
+        if geom != (self.win_len_ms, self.off_ms):
+            msg = (
+                f"snapshot of sliding stats windows (length, offset) = "
+                f"{geom} ms cannot restore a state of "
+                f"{(self.win_len_ms, self.off_ms)} ms"
+            )
+            raise ValueError(msg)
+
+    def restore_from_host(self, snap: Dict[str, Any]) -> None:
+        super().restore_from_host(snap)
+        self.win_horizon = snap["win_horizon"]
+
+    def donor_meta(self, snap: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+        self._check_geometry(snap)
+        return {"win_horizon": snap["win_horizon"]}
+
+    def merge_donors(self, parts) -> List[Dict[str, Any]]:
+        """Rescale: adopt the furthest window horizon among the donors
+        (the merged state adopts the furthest watermark as well).  A
+        pane row of a donor may lie in windows that donor has already
+        emitted, so the horizon has to come along, or those windows
+        would come out again, built from the panes that are left.  A
+        donor that is behind is first closed up to the adopted horizon
+        in a scratch state of its own; the rows of that close are
+        returned for the operator to emit.  Exact as long as no key
+        has rows in two donors with different horizons."""
+        import numpy as np
+
+        parts = [p for p in parts if len(p["keys"])]
+        if not parts:
+            return []
+        n_o = self.panes_per_offset
+        horizon = max(p["meta"]["win_horizon"] for p in parts)
+        if self.win_horizon > horizon:
+            horizon = self.win_horizon
+        out = []
+        for p in parts:
+            rows = {c: p[c] for c in _STATS_COLS}
+            behind = p["meta"]["win_horizon"]
+            if behind < horizon:
+                tmp = self._scratch_like(len(rows["keys"]))
+                tmp.win_horizon = behind
+                tmp.closed_horizon = max(behind, -(1 << 39)) * n_o
+                tmp.merge_rows(rows)
+                closed = tmp.close_below(horizon)
+                if closed is not None:
+                    out.append(closed)
+                left = tmp.snapshot_to_host()
+                if left["n"] == 0:
+                    continue
+                rows = {c: np.asarray(left[c]) for c in _STATS_COLS}
+            self.merge_rows(rows)
+        if horizon > self.win_horizon:
+            self.win_horizon = horizon
+            self.closed_horizon = horizon * n_o
+        return out
+
+    def _scratch_like(self, n_rows: int) -> "SlidingStatsAggState":
+        """An empty state of this geometry, sized for `n_rows` cells."""
+        if self.cpu:
+            return SlidingStatsAggState(
+                self.device, self.align_ms, self.win_len_ms, self.off_ms
+            )
+        slots_pow = max(10, (2 * n_rows - 1).bit_length())
+        return SlidingStatsAggState(
+            self.device, self.align_ms, self.win_len_ms, self.off_ms,
+            slots_pow=slots_pow, out_cap=self.out_cap, radix=False,
         )
 
 

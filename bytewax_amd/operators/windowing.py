@@ -873,7 +873,9 @@ def device_count() -> DeviceFoldable:
 def device_min(value_getter: Callable = _identity) -> DeviceFoldable:
     """A `fold_window` min fold that lowers to the fused stats
     kernels over RecordBatch streams (tumbling windows); pair with a
-    builder like ``lambda: float("inf")`` for the host path."""
+    builder like ``lambda: float("inf")`` for the host path.  Over a
+    `SlidingWindower` the fold runs on the host; the device route for
+    sliding windows is `keyed_stats_agg(offset=...)`."""
     return DeviceFoldable(
         "min", lambda acc, value: min(acc, value_getter(value))
     )
@@ -882,7 +884,9 @@ def device_min(value_getter: Callable = _identity) -> DeviceFoldable:
 def device_max(value_getter: Callable = _identity) -> DeviceFoldable:
     """A `fold_window` max fold that lowers to the fused stats
     kernels over RecordBatch streams (tumbling windows); pair with a
-    builder like ``lambda: -float("inf")`` for the host path."""
+    builder like ``lambda: -float("inf")`` for the host path.  Over a
+    `SlidingWindower` the fold runs on the host; the device route for
+    sliding windows is `keyed_stats_agg(offset=...)`."""
     return DeviceFoldable(
         "max", lambda acc, value: max(acc, value_getter(value))
     )
@@ -895,7 +899,9 @@ def device_mean(value_getter: Callable = _identity) -> DeviceFoldable:
 
     Host path: the accumulator is a ``(sum, count)`` pair — pair with
     a builder of ``lambda: (0, 0)``; the finisher divides at close so
-    both paths emit the mean itself.
+    both paths emit the mean itself.  Over a `SlidingWindower` the
+    fold runs on the host; the device route for sliding windows is
+    `keyed_stats_agg(offset=...)`, whose rows carry count and sum.
     """
     return DeviceFoldable(
         "mean",
@@ -940,8 +946,11 @@ class _ColumnarSpec:
         else:
             return None
         if mode in ("min", "max", "mean") and off_ms != len_ms:
-            # The stats table is tumbling-only; sliding min/max/mean
-            # stays on the host path.
+            # This lowering builds the tumbling stats state only, so a
+            # sliding min/max/mean fold stays on the host path.  The
+            # device route for those is `keyed_stats_agg(offset=...)`
+            # (`SlidingStatsAggState`); lowering onto it is open, see
+            # ROADMAP.md.
             return None
         align_ms = int(
             (windower.align_to - _EPOCH_UTC).total_seconds() * 1000
