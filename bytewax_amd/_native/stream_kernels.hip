@@ -691,6 +691,74 @@ __device__ __forceinline__ uint64_t entry_classic(
   return ((uint64_t)(wlo + entry_delta(entry)) << 32) | (entry >> 32);
 }
 
+// Compact scatter entries, the third `ev_packed` format (4 bytes),
+// written by k_radix_scatter_compact and read by k_radix_agg_compact
+// only.  With S = log2(segments) and D = S - 1 window-delta bits, the
+// event is the word x = key32 | delta << 32 of n = 32 + D bits and
+// y = mixn(x, n) a bijection of it:
+//   segment  the top S bits of y (y >> 31)
+//   entry    the low 31 bits of y; bit 31 stays 0, so all-ones is the pad
+//   LDS slot the top `seg_bits` bits of the entry
+// The segment index and the entry together are y, and mixn_inv gives
+// the key and the window back; that runs once per distinct cell at the
+// aggregation's flush, and where the scatter sends a granule to the
+// overflow spill.  mixn is three rounds of x ^= x >> ceil(n/2) and an
+// odd multiply mod 2^n, and a last xor-shift.  A shift of at least n/2
+// is its own inverse; the multiplies are undone by the constants'
+// inverses mod 2^64, which are their inverses mod 2^n as well.
+#define ENTRY_PAD32 0xFFFFFFFFu
+#define ENTRY_FMT_CLASSIC 0
+#define ENTRY_FMT_HASHED 1
+#define ENTRY_FMT_COMPACT 2
+#define MIXN_C1 0xff51afd7ed558ccdULL
+#define MIXN_C2 0xc4ceb9fe1a85ec53ULL
+#define MIXN_C3 0x9e3779b97f4a7c15ULL
+
+constexpr uint64_t mixn_inverse_of(uint64_t c) {
+  uint64_t x = c;  // Newton: correct bits double each step, 3 at start
+  for (int i = 0; i < 6; ++i) x *= 2 - c * x;
+  return x;
+}
+
+__host__ __device__ __forceinline__ uint64_t mixn(uint64_t x, int n) {
+  const uint64_t m = ((uint64_t)1 << n) - 1;
+  const int s = (n + 1) >> 1;
+  x ^= x >> s;
+  x = (x * MIXN_C1) & m;
+  x ^= x >> s;
+  x = (x * MIXN_C2) & m;
+  x ^= x >> s;
+  x = (x * MIXN_C3) & m;
+  x ^= x >> s;
+  return x;
+}
+
+__host__ __device__ __forceinline__ uint64_t mixn_inv(uint64_t y, int n) {
+  const uint64_t m = ((uint64_t)1 << n) - 1;
+  const int s = (n + 1) >> 1;
+  constexpr uint64_t i1 = mixn_inverse_of(MIXN_C1);
+  constexpr uint64_t i2 = mixn_inverse_of(MIXN_C2);
+  constexpr uint64_t i3 = mixn_inverse_of(MIXN_C3);
+  static_assert(i1 * MIXN_C1 == 1 && i2 * MIXN_C2 == 1 && i3 * MIXN_C3 == 1,
+                "inverse constants");
+  y ^= y >> s;
+  y = (y * i3) & m;
+  y ^= y >> s;
+  y = (y * i2) & m;
+  y ^= y >> s;
+  y = (y * i1) & m;
+  y ^= y >> s;
+  return y;
+}
+
+// Classic `packed` of the compact entry `e` of segment `seg`, against
+// the entry base whose low 32 bits are `wbase`.
+__device__ __forceinline__ uint64_t compact_classic(
+    uint32_t seg, uint32_t e, int n, uint32_t wbase) {
+  uint64_t x = mixn_inv(((uint64_t)seg << 31) | e, n);
+  return ((uint64_t)(wbase + (uint32_t)(x >> 32)) << 32) | (uint32_t)x;
+}
+
 // TS is int64_t (absolute ms) or int32_t (deltas from `ts_base`, the
 // wire format of the RCCL exchange — inserting the received segments
 // directly skips the int64 timestamp rebuild entirely).
@@ -1446,8 +1514,258 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged2(
   }
 }
 
+// Compact-entry sibling of k_radix_scatter_staged2<int32, .., true>
+// (ENTRY_FMT_COMPACT above): the same four phases per tile, with 4-byte
+// `stage` and `res`.  A cursor reservation is still one 64-byte line,
+// so the granule is 16 entries here: `cap`, grants and the cursor split
+// are multiples of 16 and `lpack` carries 4 residual bits.  A P4 piece
+// of 16 bytes is four entries, four adjacent lanes to a line as there.
+// Segment b's entries live at ((uint32_t*)ev_packed)[b * cap ..], so
+// the buffer is used at half its bytes.  An entry no longer carries its
+// key: a granule that the capacity split sends to the spill keeps its
+// segment index in gdst (GDC_SPILL | segment) so that P4 can rebuild
+// classic `packed`, and the final flush knows its segment anyway.
+// `dbits` is D; the host guarantees 2^(D+1) segments.
+#define SCC_GRAN 16
+#define GDC_SPILL 0x80000000u
+
+static inline size_t compact_lds_bytes(int64_t nseg, int64_t tile) {
+  size_t stage_n = (size_t)(tile + (SCC_GRAN - 1) * nseg);  // multiple of 16
+  return stage_n * 4                                // stage
+         + (size_t)nseg * SCC_GRAN * 4              // res
+         + 3 * (size_t)nseg * sizeof(int)           // res_cnt, lhist, lpack
+         + (stage_n / SCC_GRAN) * sizeof(uint32_t);  // gdst
+}
+
+template <int U = 16, int BLK = 512>
+__global__ __launch_bounds__(BLK) void k_radix_scatter_compact(
+    const int32_t* __restrict__ keys,
+    const int32_t* __restrict__ ts,
+    int64_t n,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    int dbits,
+    int64_t cap,
+    int* __restrict__ gcursors,
+    uint32_t* __restrict__ ev32,
+    int* __restrict__ ov_cursor,
+    uint64_t* __restrict__ ov_packed,
+    int64_t ov_cap,
+    unsigned long long* __restrict__ max_ts,
+    int* __restrict__ error_flag,
+    uint64_t win_m2,
+    uint64_t win_maxfast,
+    Win32 w32) {
+  constexpr int T = BLK * U;
+  constexpr int NW = BLK / WAVE;
+  // lpack: staging offset (14 bits) | residual count (4) | grant (14).
+  static_assert(T + (SCC_GRAN - 1) * BLK < (1 << 14),
+                "staging offset must fit 14 bits");
+  static_assert(T <= (1 << 13), "tile rank shares a word with the segment");
+  extern __shared__ __attribute__((aligned(16))) char smem_cc[];
+  __shared__ int s_wtot[NW];
+  const int nseg = 2 << dbits;  // host: nseg <= BLK
+  const int nbits = 32 + dbits;
+  const uint32_t dlimit = 1u << dbits;
+  const uint32_t wbase = w32.wlo + w32.qoff;
+  const int stage_n = T + (SCC_GRAN - 1) * nseg;
+  uint32_t* stage = (uint32_t*)smem_cc;            // [stage_n]
+  uint32_t* res = stage + stage_n;                 // [nseg][SCC_GRAN]
+  int* res_cnt = (int*)(res + (size_t)nseg * SCC_GRAN);  // [nseg]
+  int* lhist = res_cnt + nseg;                     // [nseg]
+  uint32_t* lpack = (uint32_t*)(lhist + nseg);     // [nseg]
+  uint32_t* gdst = lpack + nseg;                   // [stage_n / SCC_GRAN]
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wave = tid / WAVE;
+  if (tid < nseg) {
+    res_cnt[tid] = 0;
+    lhist[tid] = 0;
+  }
+  __syncthreads();
+
+  // The spill holds classic `packed` whatever the entry format is.
+  auto spill = [&](uint64_t packed) {
+    int opos = atomicAdd(ov_cursor, 1);
+    if (opos < ov_cap) ov_packed[opos] = packed;
+    else atomicOr(error_flag, 1);
+  };
+
+  // Raw columns of one tile, loaded a tile ahead, without a branch (see
+  // k_radix_scatter_staged2).
+  int32_t rk[U];
+  int32_t rt[U];
+  auto load_tile = [&](int64_t t0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      int64_t i = t0 + u * BLK + tid;
+      if (i > n - 1) i = n - 1;
+      rk[u] = keys[i];
+      rt[u] = ts[i];
+    }
+  };
+  const int64_t stride = (int64_t)gridDim.x * T;
+  // Maximum of the int32 deltas (the base is added once at the end),
+  // starting from the lane's first event when it has one.
+  int64_t local_max = 0;
+  int64_t t0 = (int64_t)blockIdx.x * T;
+  const bool seen = t0 + tid < n;
+  if (t0 < n) {
+    load_tile(t0);
+    local_max = (int64_t)rt[0];
+  }
+  for (; t0 < n; t0 += stride) {
+    uint32_t pk[U];
+    int sr[U];  // (rank << 13) | segment, or -1 when not placed
+    // P1: classify, rank.  Events of this tile that lane `tid` holds,
+    // in steps of BLK.
+    int64_t left64 = n - t0 - tid;
+    const int left = left64 > T ? T : (left64 < 0 ? 0 : (int)left64);
+    int32_t dmax = (int32_t)local_max;
+    uint32_t rare = 0;  // events for the generic path
+    // Unconditional histogram atomics, one batch (see staged2).
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool in = u * BLK < left;
+      const uint32_t d = (uint32_t)rt[u];
+      const uint32_t q = win32_div(d + w32.c, w32);
+      const uint32_t delta = q - w32.qoff;
+      const bool fits = d - w32.dlo < w32.dspan && delta < dlimit;
+      const uint64_t y = mixn(
+          ((uint64_t)(delta & (dlimit - 1)) << 32) | (uint32_t)rk[u], nbits);
+      pk[u] = (uint32_t)y & 0x7FFFFFFFu;
+      if (in && !fits) rare |= 1u << u;
+      if (in && (int32_t)d > dmax) dmax = (int32_t)d;
+      const bool ok = in && fits;
+      int b = (int)(y >> 31);  // < 2^(dbits+1) = nseg
+      int rank = atomicAdd(&lhist[b], ok ? 1 : 0);
+      sr[u] = ok ? ((rank << 13) | b) : -1;
+    }
+    local_max = dmax;
+    // Rare: one copy of the generic window code, columns read again.
+    while (rare != 0) {
+      int u = __ffs(rare) - 1;
+      rare &= rare - 1;
+      int64_t i = t0 + u * BLK + tid;
+      int64_t win = win_of((int64_t)ts[i] + ts_base, align_ms, len_ms,
+                           win_m2, win_maxfast);
+      spill(((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)keys[i]);
+    }
+    if (t0 + stride < n) load_tile(t0 + stride);
+    __syncthreads();
+    // P2a: grants, cursor reservation, wave scan of the grants.
+    int rc = 0, grant = 0, gb = 0;
+    if (tid < nseg) {
+      rc = res_cnt[tid];
+      int tot = rc + lhist[tid];
+      grant = tot & ~(SCC_GRAN - 1);
+      if (grant > 0) gb = atomicAdd(&gcursors[tid], grant);
+      res_cnt[tid] = tot - grant;
+      lhist[tid] = 0;
+    }
+    int incl = grant;
+    for (int o = 1; o < WAVE; o <<= 1) {
+      int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    if (lane == WAVE - 1) s_wtot[wave] = incl;
+    __syncthreads();
+    // P2b: staging offsets, granule destinations, residual drain.
+    int total = 0, woff = 0;
+    for (int w = 0; w < NW; ++w) {
+      int v = s_wtot[w];
+      if (w < wave) woff += v;
+      total += v;
+    }
+    const int off = woff + incl - grant;
+    // Residual drain, a wave for its own 64 segments, four segments a
+    // step: 16 adjacent lanes move one segment's slots, so `res` is read
+    // along the banks and `stage` written in runs of 16 dwords.  (One
+    // thread per segment walking its 15 slots reads and writes at a
+    // stride of 64 bytes, every lane on the same few banks.)  All
+    // fifteen slots, whatever rc is (see staged2).  nseg is a multiple
+    // of 64, so the condition is wave-uniform.
+    if (wave * WAVE < nseg) {
+      const int og = grant > 0 ? off : -1;
+      for (int k = 0; k < WAVE / 4; ++k) {
+        const int src = k * 4 + (lane >> 4);
+        const int o = __shfl(og, src);
+        const int j = lane & (SCC_GRAN - 1);
+        if (o >= 0 && j < SCC_GRAN - 1)
+          stage[o + j] = res[(size_t)(wave * WAVE + src) * SCC_GRAN + j];
+      }
+    }
+    if (tid < nseg) {
+      lpack[tid] = (uint32_t)off | ((uint32_t)rc << 14) |
+                   ((uint32_t)grant << 18);
+      if (grant > 0) {
+        for (int j = 0; j < grant; j += SCC_GRAN) {
+          int64_t gp = (int64_t)gb + j;
+          gdst[(off + j) / SCC_GRAN] =
+              gp < cap ? (uint32_t)(((int64_t)tid * cap + gp) / SCC_GRAN)
+                       : (GDC_SPILL | (uint32_t)tid);
+        }
+      }
+    }
+    __syncthreads();
+    // P3: place this tile's events (staged if granted, else residual).
+    for (int u = 0; u < U; ++u) {
+      if (sr[u] < 0) continue;
+      int b = sr[u] & ((1 << 13) - 1);
+      uint32_t w = lpack[b];
+      int vpos = (int)((w >> 14) & 15u) + (sr[u] >> 13);
+      int g = (int)(w >> 18);
+      if (vpos < g) stage[(w & ((1u << 14) - 1)) + vpos] = pk[u];
+      else res[(size_t)b * SCC_GRAN + (vpos - g)] = pk[u];
+    }
+    __syncthreads();
+    // P4: copy-out.  Piece p is entries 4p .. 4p+3; four adjacent lanes
+    // cover one 64 B line.  No barrier closes the tile (see staged2).
+    for (int p = tid; p < total / 4; p += BLK) {
+      uint4 v = *(const uint4*)(stage + 4 * p);
+      uint32_t d = gdst[p / 4];
+      if ((d & GDC_SPILL) == 0) {
+        *(uint4*)(ev32 + (int64_t)d * SCC_GRAN + 4 * (p & 3)) = v;
+      } else {
+        const uint32_t seg = d & ~GDC_SPILL;
+        const uint32_t e[4] = {v.x, v.y, v.z, v.w};
+        for (int j = 0; j < 4; ++j)
+          if (e[j] != ENTRY_PAD32)
+            spill(compact_classic(seg, e[j], nbits, wbase));
+      }
+    }
+  }
+  __syncthreads();
+  // Final flush: pad-filled granules, like the default staged.
+  if (tid < nseg) {
+    int rc = res_cnt[tid];
+    if (rc > 0) {
+      int gb = atomicAdd(&gcursors[tid], SCC_GRAN);
+      for (int j = 0; j < SCC_GRAN; ++j) {
+        uint32_t e = j < rc ? res[(size_t)tid * SCC_GRAN + j] : ENTRY_PAD32;
+        int64_t gp = (int64_t)gb + j;
+        if (gp < cap) ev32[(int64_t)tid * cap + gp] = e;
+        else if (e != ENTRY_PAD32)
+          spill(compact_classic((uint32_t)tid, e, nbits, wbase));
+      }
+    }
+  }
+  local_max = seen ? local_max + ts_base : 0;
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    int64_t other = __shfl_down((long long)local_max, off);
+    if (other > local_max) local_max = other;
+  }
+  if ((threadIdx.x & (WAVE - 1)) == 0 && local_max > 0) {
+    atomicMax(max_ts, (unsigned long long)local_max);
+  }
+}
+
 // Aggregate the overflow spill straight into the table (tiny for
-// uniform keys).
+// uniform keys).  `spill_total` (may be null) is a running total of
+// the spilled events, which the state reads at a close to see whether
+// a stream lives on this slow path; launches on one table are ordered,
+// so one thread adds with a plain add.
 template <int MODE>
 __global__ void k_overflow_agg(
     const uint64_t* __restrict__ ov_packed,
@@ -1458,9 +1776,12 @@ __global__ void k_overflow_agg(
     unsigned long long* __restrict__ tvals,
     uint64_t mask,
     int region_bits,
-    int* __restrict__ error_flag) {
+    int* __restrict__ error_flag,
+    unsigned long long* __restrict__ spill_total) {
   int64_t n = *ov_cursor;
   if (n > ov_cap) n = ov_cap;
+  if (spill_total != nullptr && blockIdx.x == 0 && threadIdx.x == 0 && n > 0)
+    *spill_total += (unsigned long long)n;
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t stride = gridDim.x * (int64_t)blockDim.x;
   for (; i < n; i += stride) {
@@ -1832,6 +2153,185 @@ __global__ __launch_bounds__(BLK, BLK == 1024 ? 8 : 4) void k_radix_agg_count(
       uint64_t packed = ((uint64_t)win << 32) | (c >> 32);
       if (!hash_add(tkeys, tvals, mask, region_bits, packed,
                     c & 0x0FFFFFFFULL)) {
+        atomicOr(error_flag, 1);
+      }
+    }
+  }
+}
+
+// COUNT segment aggregation for compact entries (ENTRY_FMT_COMPACT).
+//
+// The structure of k_radix_agg_count with 4-byte entries: a register
+// double buffer of R 16-byte loads (four entries each), head and tail
+// peeling of up to three entries, the first probe of a chunk's 4R
+// entries batched, one probe / CAS loop per chunk for what is left.
+// A cell is entry << 32 | count32 and all-ones is empty: bit 31 of an
+// entry is 0, so no cell equals it.  The entry is the whole tag (the
+// block's segment index supplies the rest of the hash), the slot its
+// top `lds_bits` bits; there is no window range, and an entry goes
+// straight to the table only when the LDS table is full.  The flush
+// inverts the mixer once per cell to rebuild classic `packed` for
+// hash_add.  Segments are slices of the mixn hash, not of the table:
+// the flush of a block lands anywhere in the table, which hash_add's
+// atomics make correct.
+template <int BLK, int R>
+__global__ __launch_bounds__(BLK, BLK == 1024 ? 8 : 4) void k_radix_agg_compact(
+    const uint32_t* __restrict__ ev32,
+    const int* __restrict__ counts,
+    int64_t cap,
+    uint64_t* __restrict__ tkeys,
+    unsigned long long* __restrict__ tvals,
+    uint64_t mask,
+    int region_bits,
+    int lds_bits,
+    int* __restrict__ error_flag,
+    uint32_t wbase,
+    int dbits) {
+  extern __shared__ char smem[];
+  unsigned long long* cells = (unsigned long long*)smem;
+  const int region = 1 << lds_bits;
+  const uint32_t lmask = (uint32_t)region - 1;
+  const int sshift = 31 - lds_bits;
+  const int nbits = 32 + dbits;
+  const int b = blockIdx.x;
+  int cnt = counts[b];
+  if (cnt > (int)cap) cnt = (int)cap;
+  if (cnt <= 0) return;  // block-uniform
+  for (int s = threadIdx.x; s < region / 2; s += BLK) {
+    ((agg_u64x2*)cells)[s] = agg_u64x2{EMPTY_SLOT, EMPTY_SLOT};
+  }
+  const uint32_t* seg = ev32 + (int64_t)b * cap;
+  __syncthreads();
+
+  auto escape = [&](uint32_t e) {
+    if (!hash_add(tkeys, tvals, mask, region_bits,
+                  compact_classic((uint32_t)b, e, nbits, wbase), 1ULL)) {
+      atomicOr(error_flag, 1);
+    }
+  };
+  // Probe / claim loop over a lane's leftovers (see k_radix_agg_count).
+  auto drain = [&](uint32_t pend, auto entry, auto start, auto skipped) {
+    uint32_t tag = 0;
+    uint32_t lh = 0;
+    int left = 0;  // probe steps before the table counts as full
+    while (left != 0 || pend != 0) {
+      if (left == 0) {
+        int e = __ffs(pend) - 1;
+        pend &= pend - 1;
+        tag = entry(e);
+        lh = start(e);
+        left = region - (skipped(e) ? 1 : 0);
+      }
+      unsigned long long cur = cells[lh];
+      if (cur == EMPTY_SLOT) {
+        cur = atomicCAS(&cells[lh], EMPTY_SLOT,
+                        (unsigned long long)tag << 32);
+        if (cur == EMPTY_SLOT) cur = (unsigned long long)tag << 32;
+      }
+      if ((uint32_t)(cur >> 32) == tag) {
+        atomicAdd((unsigned int*)&cells[lh], 1u);
+        left = 0;
+      } else {
+        lh = (lh + 1) & lmask;
+        if (--left == 0) escape(tag);  // LDS table full
+      }
+    }
+  };
+  auto add_one = [&](uint32_t e) {
+    if (e == ENTRY_PAD32) return;  // scatter pad
+    drain(
+        1u, [&](int) { return e; }, [&](int) { return e >> sshift; },
+        [&](int) { return false; });
+  };
+
+  // Head/tail entries outside the 16-byte-aligned vector body.
+  int head = (int)(((16 - ((uintptr_t)seg & 15)) & 15) >> 2);
+  if (head > cnt) head = cnt;
+  const int nvec = (cnt - head) >> 2;
+  const int tail = head + 4 * nvec;  // cnt - 3 .. cnt
+  if (threadIdx.x == 0)
+    for (int j = 0; j < head; ++j) add_one(seg[j]);
+  if (threadIdx.x == BLK - 1)
+    for (int j = tail; j < cnt; ++j) add_one(seg[j]);
+
+  const uint4* vseg = (const uint4*)(seg + head);
+  constexpr int chunk = R * BLK;
+  constexpr int E = 4 * R;
+  uint4 cur_p[R], nxt_p[R];
+  auto fetch = [&](uint4 (&bp)[R], int base) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      int v = base + r * BLK + (int)threadIdx.x;
+      if (v < nvec) bp[r] = vseg[v];
+      else bp[r] = uint4{ENTRY_PAD32, ENTRY_PAD32, ENTRY_PAD32, ENTRY_PAD32};
+    }
+  };
+  auto pick = [&](int e) {
+    const uint4& q = cur_p[e >> 2];
+    return (e & 3) == 0 ? q.x : (e & 3) == 1 ? q.y : (e & 3) == 2 ? q.z : q.w;
+  };
+  fetch(cur_p, 0);
+  for (int base = 0; base < nvec; base += chunk) {
+    // Issue the next chunk's loads before touching the LDS table.
+    if (base + chunk < nvec) fetch(nxt_p, base + chunk);
+    uint32_t slot[E];
+    unsigned long long first[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      // A pad's slot is in range as well (bit 31 is shifted in).
+      slot[e] = (pick(e) >> sshift) & lmask;
+      first[e] = cells[slot[e]];
+    }
+    uint32_t pend = 0, moved = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      uint32_t en = pick(e);
+      if (en == ENTRY_PAD32) continue;  // scatter pad
+      if ((uint32_t)(first[e] >> 32) == en) {
+        atomicAdd((unsigned int*)&cells[slot[e]], 1u);
+      } else {
+        pend |= 1u << e;
+        if (first[e] != EMPTY_SLOT) {
+          // Another cell's: start one further on.
+          slot[e] = (slot[e] + 1) & lmask;
+          moved |= 1u << e;
+        }
+      }
+    }
+    if (pend != 0) {
+      drain(
+          pend,
+          [&](int e) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+              if (j == e) v = pick(j);
+            }
+            return v;
+          },
+          [&](int e) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+              if (j == e) v = slot[j];
+            }
+            return v;
+          },
+          [&](int e) { return ((moved >> e) & 1u) != 0; });
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) cur_p[r] = nxt_p[r];
+  }
+  __syncthreads();
+
+  // Flush each cell once: invert the mixer, rebuild `packed`.
+  for (int s = threadIdx.x; s < region; s += BLK) {
+    unsigned long long c = cells[s];
+    if (c != EMPTY_SLOT) {
+      if (!hash_add(tkeys, tvals, mask, region_bits,
+                    compact_classic((uint32_t)b, (uint32_t)(c >> 32), nbits,
+                                    wbase),
+                    c & 0xFFFFFFFFULL)) {
         atomicOr(error_flag, 1);
       }
     }
@@ -3841,10 +4341,15 @@ static bool agg_wide_env() {
   return s != nullptr && s[0] == 'w';
 }
 
-// BYTEWAX_ENTRIES=classic keeps classic scatter entries (A/B, tests).
+// BYTEWAX_ENTRIES=classic keeps classic scatter entries, =hashed stops
+// at the 8-byte hashed ones (A/B, tests).
 static bool entries_classic_env() {
   const char* s = std::getenv("BYTEWAX_ENTRIES");
   return s != nullptr && s[0] == 'c';
+}
+static bool entries_hashed_env() {
+  const char* s = std::getenv("BYTEWAX_ENTRIES");
+  return s != nullptr && s[0] == 'h';
 }
 
 // Launch shape of k_radix_scatter_staged2 for `nseg` segments; false
@@ -3881,16 +4386,30 @@ static bool count_agg_compact(int64_t cap, int seg_bits) {
 // plans here and hands the plan to both, so the two launches cannot
 // disagree.
 struct CountEntries {
-  bool hashed = false;
+  bool hashed = false;  // hashed or compact: an entry base exists
+  int dbits = 0;        // compact entries: their window-delta bits D
   int64_t W = 0;      // window id that y = 0 of the first segment is in
   uint32_t qoff = 0;  // entry base = W + qoff
   uint32_t dm = 0;    // divider for len_ms
   int sh1 = 0, sh2 = 0;
+  bool compact() const { return dbits > 0; }
+  int fmt() const {
+    return compact() ? ENTRY_FMT_COMPACT
+                     : hashed ? ENTRY_FMT_HASHED : ENTRY_FMT_CLASSIC;
+  }
   // What launch_count_agg is told: the entry base, or "classic".
   int64_t agg_w() const {
     return hashed ? W + (int64_t)qoff : ENTRY_W_CLASSIC;
   }
 };
+
+// Window-delta bits of compact entries over `nseg` segments (nseg a
+// power of two, at least 128).
+static int compact_dbits(int64_t nseg) {
+  int s = 0;
+  while (((int64_t)1 << s) < nseg) ++s;
+  return s - 1;
+}
 
 // Hashed entries need: the staged2 scatter in its default tile shape,
 // the compact-cell aggregation, timestamps that are int32 deltas from a
@@ -3905,10 +4424,15 @@ struct CountEntries {
 // The entry base lies 2^18 windows before the window of `first_base`
 // (but not before W), so the 19-bit entry delta reaches about as far
 // back as forward.
+//
+// Compact entries need all of that and at least 128 segments (D >= 6);
+// their base lies 2^(D-1) windows before the window of `first_base`.
+// `allow_compact` is false for a caller whose aggregation side cannot
+// be told the format, and for a state that has demoted itself.
 static CountEntries plan_count_entries(
     bool staged_count, int64_t xf, const void* evp, int64_t nseg,
     int64_t cap, int seg_bits, bool ts_i32, int64_t align_ms,
-    int64_t len_ms, int64_t first_base) {
+    int64_t len_ms, int64_t first_base, bool allow_compact = true) {
   CountEntries ce;
   if (!staged_count || !ts_i32 || entries_classic_env() ||
       !count_staged2_ok(xf, evp, nseg) || !count_agg_compact(cap, seg_bits))
@@ -3933,7 +4457,13 @@ static CountEntries plan_count_entries(
   ce.sh1 = l < 1 ? l : 1;
   ce.sh2 = l > 1 ? l - 1 : 0;
   int64_t q0 = (int64_t)((num - w * len_ms + ((__int128)1 << 31)) / len_ms);
-  ce.qoff = q0 > (1 << 18) ? (uint32_t)(q0 - (1 << 18)) : 0u;
+  int64_t back = (int64_t)1 << 18;
+  if (allow_compact && !entries_hashed_env() && nseg >= 128 &&
+      (nseg & (nseg - 1)) == 0 && (cap & ~(int64_t)(SCC_GRAN - 1)) > 0) {
+    ce.dbits = compact_dbits(nseg);
+    back = (int64_t)1 << (ce.dbits - 1);
+  }
+  ce.qoff = q0 > back ? (uint32_t)(q0 - back) : 0u;
   return ce;
 }
 
@@ -4032,6 +4562,23 @@ static void launch_count_staged(
       if (ce.hashed) {
         // Planned for the default shape only.
         w32 = make_win32(ce, ts_base, align_ms, len_ms);
+        if (ce.compact()) {
+          TORCH_CHECK(nseg == ((int64_t)2 << ce.dbits) && nseg <= 512,
+                      "compact entries planned for another segment count");
+          int64_t gs = (n + 8191) / 8192;
+          unsigned cap_gs = env_blocks > 0 ? (unsigned)env_blocks : cus;
+          if (gs > (int64_t)cap_gs) gs = cap_gs;
+          if (gs < 1) gs = 1;
+          // Granules of 16 entries: both launches round `cap` down.
+          hipLaunchKernelGGL(
+              (k_radix_scatter_compact<16, 512>), dim3((unsigned)gs),
+              dim3(512), compact_lds_bytes(nseg, 8192), stream, keys, ts, n,
+              align_ms, len_ms, ts_base, ce.dbits,
+              cap & ~(int64_t)(SCC_GRAN - 1), gcur, (uint32_t*)evp, ovc, ovp,
+              ov_cap, max_ts, err, win_m2, win_maxfast, w32);
+          HIP_CHECK(hipGetLastError());
+          return;
+        }
         go((k_radix_scatter_staged2<TSV, 16, 512, true>), 512, 16, cus, lds,
            w32);
         return;
@@ -4081,12 +4628,37 @@ static void launch_count_agg(
     hipStream_t stream, const uint64_t* evp, const int* gcur, int64_t cap,
     uint64_t* tkeys, unsigned long long* tvals, uint64_t mask,
     int region_bits, int seg_bits, int64_t nseg, int* err,
-    int64_t entry_w) {
+    int64_t entry_w, int entry_fmt) {
   // `entry_w`: CountEntries::agg_w() of the scatter call that filled
-  // `evp`: its entry base when the entries are hashed, else
-  // ENTRY_W_CLASSIC.
+  // `evp`: its entry base when the entries are hashed or compact, else
+  // ENTRY_W_CLASSIC.  `entry_fmt`: its CountEntries::fmt().
   const bool hashed = entry_w != ENTRY_W_CLASSIC;
   const uint32_t wlo = hashed ? (uint32_t)(uint64_t)entry_w : 0u;
+  TORCH_CHECK(hashed == (entry_fmt != ENTRY_FMT_CLASSIC),
+              "entry format and entry base disagree");
+  if (entry_fmt == ENTRY_FMT_COMPACT) {
+    TORCH_CHECK(count_agg_compact(cap, seg_bits) && nseg >= 128 &&
+                    (nseg & (nseg - 1)) == 0,
+                "compact entries need the compact-cell aggregation and a "
+                "power-of-two segment count of at least 128");
+    auto go = [&](auto kern, int threads) {
+      hipLaunchKernelGGL(
+          kern, dim3((unsigned)nseg), dim3((unsigned)threads),
+          (size_t)8 << seg_bits, stream, (const uint32_t*)evp, gcur,
+          cap & ~(int64_t)(SCC_GRAN - 1), tkeys, tvals, mask, region_bits,
+          seg_bits, err, wlo, compact_dbits(nseg));
+      HIP_CHECK(hipGetLastError());
+    };
+    int r = 2;
+    if (const char* e = std::getenv("BYTEWAX_AGG_R")) r = atoi(e);
+    if (seg_bits >= 12) {
+      if (r == 1) go((k_radix_agg_compact<1024, 1>), 1024);
+      else go((k_radix_agg_compact<1024, 2>), 1024);
+    } else {
+      go((k_radix_agg_compact<256, 2>), 256);
+    }
+    return;
+  }
   if (count_agg_compact(cap, seg_bits)) {
     auto go = [&](auto kern, int threads) {
       hipLaunchKernelGGL(
@@ -4123,6 +4695,15 @@ static void launch_count_agg(
 // chip and costs nothing when the spill is empty.
 static dim3 overflow_agg_grid() { return dim3(device_cu_count()); }
 
+// The optional running total of spilled events (int64 [1]).
+static unsigned long long* spill_total_ptr(
+    const c10::optional<torch::Tensor>& t) {
+  if (!t.has_value()) return nullptr;
+  check_dev(*t, torch::kInt64, "spill_total");
+  TORCH_CHECK(t->numel() >= 1, "spill_total must hold one int64");
+  return (unsigned long long*)t->data_ptr<int64_t>();
+}
+
 static void radix_window_insert_impl(
     torch::Tensor keys,
     torch::Tensor ts,
@@ -4145,7 +4726,9 @@ static void radix_window_insert_impl(
     int64_t off_ms,  // sliding stride; 0 or == len_ms for tumbling
     std::vector<int64_t> seg_counts,
     std::vector<int64_t> seg_bases,
-    const LateSink* late) {
+    const LateSink* late,
+    c10::optional<torch::Tensor> spill_total = c10::nullopt,
+    bool allow_compact = true) {
   if (off_ms <= 0) off_ms = len_ms;
   TORCH_CHECK(off_ms <= len_ms, "window offset must be <= length");
   check_dev(keys, torch::kInt32, "keys");
@@ -4275,7 +4858,7 @@ static void radix_window_insert_impl(
   const CountEntries ce = plan_count_entries(
       kind == SCAT_STAGED && mode == AGG_COUNT && late == nullptr, xf,
       ev_packed.data_ptr<int64_t>(), nseg, cap, seg_bits, seg32 || ts32,
-      align_ms, len_ms, segs[0].base);
+      align_ms, len_ms, segs[0].base, allow_compact);
   unsigned scat_threads = 256;
   // `extra`: the trailing late-tracking arguments of the staged and
   // fixed kernels.
@@ -4401,7 +4984,7 @@ static void radix_window_insert_impl(
         (uint64_t*)tkeys.data_ptr<int64_t>(),
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
         (int)region_bits, seg_bits, nseg, error_flag.data_ptr<int32_t>(),
-        ce.agg_w());
+        ce.agg_w(), ce.fmt());
   } else {
     agg(k_radix_agg<AGG_SUM>);
   }
@@ -4414,7 +4997,8 @@ static void radix_window_insert_impl(
         ov_cursor.data_ptr<int32_t>(), ov_packed.numel(),
         (uint64_t*)tkeys.data_ptr<int64_t>(),
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
-        (int)region_bits, error_flag.data_ptr<int32_t>());
+        (int)region_bits, error_flag.data_ptr<int32_t>(),
+        spill_total_ptr(spill_total));
   };
   if (mode == AGG_COUNT) ov(k_overflow_agg<AGG_COUNT>);
   else ov(k_overflow_agg<AGG_SUM>);
@@ -4441,12 +5025,16 @@ void radix_window_insert(
     int64_t region_bits,
     int64_t off_ms = 0,  // sliding stride; 0 or == len_ms for tumbling
     std::vector<int64_t> seg_counts = {},
-    std::vector<int64_t> seg_bases = {}) {
+    std::vector<int64_t> seg_bases = {},
+    // Running total of spilled events (int64 [1]), and whether compact
+    // entries may be planned (a demoted state says no).
+    c10::optional<torch::Tensor> spill_total = c10::nullopt,
+    bool compact = true) {
   radix_window_insert_impl(
       keys, ts, vals, tkeys, tvals, max_ts, error_flag, gcursors, ev_packed,
       ev_vals, ov_cursor, ov_packed, ov_vals, align_ms, len_ms, mode, ts_base,
       region_bits, off_ms, std::move(seg_counts), std::move(seg_bases),
-      nullptr);
+      nullptr, std::move(spill_total), compact);
 }
 
 // Late-tracking form of radix_window_insert (unsegmented batches
@@ -4494,8 +5082,12 @@ void radix_window_insert_late(
 // events, which keeps it per-state and lets the exchange wait be
 // recorded on the side stream only.
 // Returns what radix_agg_only must be told about the entries: the
-// call's entry base when they are hashed, else ENTRY_W_CLASSIC.
-int64_t radix_scatter_only(
+// call's entry base when they are hashed, else ENTRY_W_CLASSIC.  With
+// `compact` the call may write compact entries and returns the pair
+// (entry base, ENTRY_FMT_*) instead, both for radix_agg_only; without
+// it the entries are never compact and the base alone says which of
+// the other two formats they have.
+pybind11::object radix_scatter_only(
     torch::Tensor keys,
     torch::Tensor ts,
     c10::optional<torch::Tensor> vals,
@@ -4515,7 +5107,12 @@ int64_t radix_scatter_only(
     int64_t region_bits,
     int64_t off_ms,
     std::vector<int64_t> seg_counts,
-    std::vector<int64_t> seg_bases) {
+    std::vector<int64_t> seg_bases,
+    bool compact = false) {
+  auto result = [&](const CountEntries& ce) -> pybind11::object {
+    if (!compact) return pybind11::int_(ce.agg_w());
+    return pybind11::make_tuple(ce.agg_w(), ce.fmt());
+  };
   if (off_ms <= 0) off_ms = len_ms;
   TORCH_CHECK(off_ms <= len_ms, "window offset must be <= length");
   check_dev(keys, torch::kInt32, "keys");
@@ -4590,7 +5187,7 @@ int64_t radix_scatter_only(
       gcursors.data_ptr<int32_t>(), 0, (size_t)nseg * sizeof(int), stream));
   HIP_CHECK(hipMemsetAsync(
       ov_cursor.data_ptr<int32_t>(), 0, sizeof(int), stream));
-  if (n == 0) return ENTRY_W_CLASSIC;
+  if (n == 0) return result(CountEntries{});
 
   struct Seg {
     int64_t off, n, base;
@@ -4605,11 +5202,11 @@ int64_t radix_scatter_only(
   } else {
     segs.push_back({0, n, ts_base});
   }
-  if (segs.empty()) return ENTRY_W_CLASSIC;
+  if (segs.empty()) return result(CountEntries{});
   const CountEntries ce = plan_count_entries(
       kind == SCAT_STAGED && mode == AGG_COUNT, xf,
       ev_packed.data_ptr<int64_t>(), nseg, cap, seg_bits, seg32 || ts32,
-      align_ms, len_ms, segs[0].base);
+      align_ms, len_ms, segs[0].base, compact);
   unsigned scat_threads = 256;
   // `extra`: the trailing late-tracking arguments of the staged and
   // fixed kernels (always off on this path).
@@ -4670,11 +5267,12 @@ int64_t radix_scatter_only(
     if (seg32 || ts32) scat_any(ts.data_ptr<int32_t>(), sg);
     else scat_any(ts.data_ptr<int64_t>(), sg);
   }
-  return ce.agg_w();
+  return result(ce);
 }
 
-// `entry_w`: what the radix_scatter_only call that filled these buffers
-// returned.
+// `entry_w`, `entry_fmt`: what the radix_scatter_only call that filled
+// these buffers returned.  Without `entry_fmt` the base alone tells
+// classic from hashed entries.
 void radix_agg_only(
     torch::Tensor tkeys,
     torch::Tensor tvals,
@@ -4687,7 +5285,13 @@ void radix_agg_only(
     torch::Tensor ov_vals,
     int64_t mode,
     int64_t region_bits,
-    int64_t entry_w = ENTRY_W_CLASSIC) {
+    int64_t entry_w = ENTRY_W_CLASSIC,
+    int64_t entry_fmt = -1,
+    c10::optional<torch::Tensor> spill_total = c10::nullopt) {
+  if (mode != AGG_COUNT) entry_w = ENTRY_W_CLASSIC;
+  if (entry_fmt < 0 || mode != AGG_COUNT)
+    entry_fmt =
+        entry_w != ENTRY_W_CLASSIC ? ENTRY_FMT_HASHED : ENTRY_FMT_CLASSIC;
   int64_t nslots = tkeys.numel();
   int64_t nb = nslots >> region_bits;
   auto stream = at::hip::getCurrentHIPStream();
@@ -4746,7 +5350,7 @@ void radix_agg_only(
         (uint64_t*)tkeys.data_ptr<int64_t>(),
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
         (int)region_bits, seg_bits, nseg, error_flag.data_ptr<int32_t>(),
-        mode == AGG_COUNT ? entry_w : ENTRY_W_CLASSIC);
+        entry_w, (int)entry_fmt);
   } else {
     agg(k_radix_agg<AGG_SUM>);
   }
@@ -4758,7 +5362,8 @@ void radix_agg_only(
         ov_cursor.data_ptr<int32_t>(), ov_packed.numel(),
         (uint64_t*)tkeys.data_ptr<int64_t>(),
         (unsigned long long*)tvals.data_ptr<int64_t>(), mask,
-        (int)region_bits, error_flag.data_ptr<int32_t>());
+        (int)region_bits, error_flag.data_ptr<int32_t>(),
+        spill_total_ptr(spill_total));
   };
   if (mode == AGG_COUNT) ov(k_overflow_agg<AGG_COUNT>);
   else ov(k_overflow_agg<AGG_SUM>);
@@ -6545,14 +7150,15 @@ int64_t native_run_window_steps(
             (uint64_t*)cur_k.data_ptr<int64_t>(),
             (unsigned long long*)cur_v.data_ptr<int64_t>(), mask,
             (int)region_bits, seg_bits, nseg,
-            error_flag.data_ptr<int32_t>(), ce.agg_w());
+            error_flag.data_ptr<int32_t>(), ce.agg_w(), ce.fmt());
         hipLaunchKernelGGL(
             k_overflow_agg<AGG_COUNT>, overflow_agg_grid(), block, 0, stream,
             (const uint64_t*)ovp.data_ptr<int64_t>(),
             (const int64_t*)nullptr, ovc.data_ptr<int32_t>(), ovp.numel(),
             (uint64_t*)cur_k.data_ptr<int64_t>(),
             (unsigned long long*)cur_v.data_ptr<int64_t>(), mask,
-            (int)region_bits, error_flag.data_ptr<int32_t>());
+            (int)region_bits, error_flag.data_ptr<int32_t>(),
+            (unsigned long long*)nullptr);
         HIP_CHECK(hipEventRecord(ev_ag[par], stream));
       } else if (use_radix) {
         radix_window_insert(
@@ -7056,7 +7662,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "scatter (COUNT mode)");
   m.def("radix_scatter_only", &radix_scatter_only,
         "Scatter stage of the radix insert on the current stream; returns "
-        "the entry base for radix_agg_only");
+        "the entry base for radix_agg_only, or with compact=True the pair "
+        "(entry base, entry format)",
+        pybind11::arg("keys"), pybind11::arg("ts"), pybind11::arg("vals"),
+        pybind11::arg("max_ts"), pybind11::arg("error_flag"),
+        pybind11::arg("gcursors"), pybind11::arg("ev_packed"),
+        pybind11::arg("ev_vals"), pybind11::arg("ov_cursor"),
+        pybind11::arg("ov_packed"), pybind11::arg("ov_vals"),
+        pybind11::arg("nslots"), pybind11::arg("align_ms"),
+        pybind11::arg("len_ms"), pybind11::arg("mode"),
+        pybind11::arg("ts_base"), pybind11::arg("region_bits"),
+        pybind11::arg("off_ms"), pybind11::arg("seg_counts"),
+        pybind11::arg("seg_bases"), pybind11::arg("compact") = false);
   m.def("radix_agg_only", &radix_agg_only,
         "Aggregation stage of the radix insert on the current stream",
         pybind11::arg("tkeys"), pybind11::arg("tvals"),
@@ -7065,7 +7682,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("ov_cursor"), pybind11::arg("ov_packed"),
         pybind11::arg("ov_vals"), pybind11::arg("mode"),
         pybind11::arg("region_bits"),
-        pybind11::arg("entry_w") = (int64_t)ENTRY_W_CLASSIC);
+        pybind11::arg("entry_w") = (int64_t)ENTRY_W_CLASSIC,
+        pybind11::arg("entry_fmt") = (int64_t)-1,
+        pybind11::arg("spill_total") = pybind11::none());
   m.def("window_agg_insert_late", &window_agg_insert_late,
         "Single-pass window insert that diverts events below the late "
         "cutoff to a late buffer");
@@ -7079,7 +7698,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Radix stats insert that diverts events below the late cutoff "
         "to a late buffer");
   m.def("radix_window_insert", &radix_window_insert,
-        "Radix-partitioned LDS-staged keyed window aggregation");
+        "Radix-partitioned LDS-staged keyed window aggregation",
+        pybind11::arg("keys"), pybind11::arg("ts"), pybind11::arg("vals"),
+        pybind11::arg("tkeys"), pybind11::arg("tvals"),
+        pybind11::arg("max_ts"), pybind11::arg("error_flag"),
+        pybind11::arg("gcursors"), pybind11::arg("ev_packed"),
+        pybind11::arg("ev_vals"), pybind11::arg("ov_cursor"),
+        pybind11::arg("ov_packed"), pybind11::arg("ov_vals"),
+        pybind11::arg("align_ms"), pybind11::arg("len_ms"),
+        pybind11::arg("mode"), pybind11::arg("ts_base"),
+        pybind11::arg("region_bits"), pybind11::arg("off_ms"),
+        pybind11::arg("seg_counts"), pybind11::arg("seg_bases"),
+        pybind11::arg("spill_total") = pybind11::none(),
+        pybind11::arg("compact") = true);
   m.def("close_migrate", &close_migrate,
         "Window close with reclamation: emit closed cells and migrate "
         "live cells into a fresh table");

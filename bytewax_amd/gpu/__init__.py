@@ -21,6 +21,7 @@ folds) for device-resolvable aggregations; arbitrary Python logic
 stays on the host path.
 """
 
+import logging
 from dataclasses import dataclass
 from datetime import datetime, timezone
 from typing import Any, Dict, Optional, Tuple
@@ -32,6 +33,14 @@ EPOCH_UTC = datetime(1970, 1, 1, tzinfo=timezone.utc)
 
 AGG_COUNT = 0
 AGG_SUM = 1
+# A keyed window state gives up compact scatter entries when more than
+# one event in this many went through the overflow spill between two
+# closes.  A policy constant: a spilled event costs about 35 times an
+# event on the fast path (profiles/r07_compact_entries.md).
+SPILL_DEMOTE_SHARE = 64
+# What radix_scatter_only returns in place of an entry base when it
+# wrote classic entries.
+ENTRY_W_CLASSIC = -(1 << 63)
 
 _INT64_MAX = (1 << 63) - 1
 
@@ -588,6 +597,20 @@ class WindowAggState:
                 1, dtype=torch.int32, device=device
             )
             self._alloc_rx(max(max_batch, 1))
+            # Compact scatter entries reach 2^(D-1) windows to either
+            # side of a batch's first base; what lies beyond is spilled
+            # and aggregated one event at a time.  The kernels keep a
+            # running total of spilled events, read at a close next to
+            # `out_n`; a stream that spills more than 1 event in
+            # SPILL_DEMOTE_SHARE since the previous close keeps the
+            # 8-byte hashed entries (2^18 windows) from then on.
+            self.spill_total = torch.zeros(
+                1, dtype=torch.int64, device=device
+            )
+            self.compact_ok = True
+            self._spill_seen = 0
+            self._ins_since_close = 0
+            self._spill_pin = None
         if self.cpu:
             # Host twin of the device table: used for CPU-only test
             # runs of the columnar path (gloo, no GPU).  Not a
@@ -775,7 +798,10 @@ class WindowAggState:
                 self.off_ms,
                 [],
                 [],
+                self.spill_total,
+                self.compact_ok,
             )
+            self._ins_since_close += len(batch)
         else:
             self.k.window_agg_insert(
                 batch.keys,
@@ -884,9 +910,11 @@ class WindowAggState:
         self._pipe_parity = 0
         self._ev_sc = [torch.cuda.Event(), torch.cuda.Event()]
         # What each parity's scatter said about its entries (the entry
-        # base of hashed entries, or the "classic" marker): host-known,
-        # so the aggregation needs no device word and no sync.
+        # base of hashed or compact entries, or the "classic" marker,
+        # and which of the three formats they have): host-known, so the
+        # aggregation needs no device word and no sync.
         self._ev_w = [None, None]
+        self._ev_fmt = [None, None]
         self._ev_ag = [torch.cuda.Event(), torch.cuda.Event()]
         self._ag_recorded = [False, False]
         if not hasattr(self, "rx_packed2"):
@@ -961,7 +989,12 @@ class WindowAggState:
             ts.record_stream(self._sc_stream)
             if vals is not None:
                 vals.record_stream(self._sc_stream)
-            self._ev_w[par] = self.k.radix_scatter_only(
+            self._ins_since_close += n
+            # With `compact` the call answers (entry base, format);
+            # without it the base alone, which tells hashed entries
+            # from classic ones.
+            compact = self.compact_ok
+            said = self.k.radix_scatter_only(
                 keys,
                 ts,
                 vals,
@@ -977,7 +1010,11 @@ class WindowAggState:
                 self.off_ms,
                 list(seg_counts),
                 [int(b) for b in seg_bases],
+                compact,
             )
+            if not compact:
+                said = (said, 0 if said == ENTRY_W_CLASSIC else 1)
+            self._ev_w[par], self._ev_fmt[par] = said
             self._ev_sc[par].record(self._sc_stream)
         cur.wait_event(self._ev_sc[par])
         self.k.radix_agg_only(
@@ -988,6 +1025,8 @@ class WindowAggState:
             self.mode,
             self.region_bits,
             self._ev_w[par],
+            self._ev_fmt[par],
+            self.spill_total,
         )
         self._ev_ag[par].record(cur)
         self._ag_recorded[par] = True
@@ -1032,7 +1071,10 @@ class WindowAggState:
             self.off_ms,
             lz.seg_counts,
             lz.seg_bases,
+            self.spill_total,
+            self.compact_ok,
         )
+        self._ins_since_close += n
         if lz.max_ts is not None and lz.max_ts > self.max_ts_host:
             self.max_ts_host = lz.max_ts
 
@@ -1079,6 +1121,8 @@ class WindowAggState:
         _check_error_flag(
             int(self.error_flag.item()), "keyed window state table"
         )
+        if self.radix:
+            self._note_spill(int(self.spill_total.item()))
         if n == 0:
             return None
         return RecordBatch(
@@ -1086,6 +1130,28 @@ class WindowAggState:
             self.out_wins[:n].to(torch.int64) * self.off_ms + self.align_ms,
             self.out_vals[:n].clone(),
         )
+
+    def _note_spill(self, total: int) -> None:
+        """Demote the state to hashed entries when the events spilled
+        since the previous close exceed 1/SPILL_DEMOTE_SHARE of the
+        events inserted since then (sticky, logged once)."""
+        spilled = total - self._spill_seen
+        inserted = self._ins_since_close
+        self._spill_seen = total
+        self._ins_since_close = 0
+        if (
+            self.compact_ok
+            and inserted > 0
+            and spilled * SPILL_DEMOTE_SHARE > inserted
+        ):
+            self.compact_ok = False
+            logging.getLogger(__name__).warning(
+                "keyed window state: %d of %d events since the last close "
+                "went through the overflow spill; keeping 8-byte hashed "
+                "scatter entries from here on",
+                spilled,
+                inserted,
+            )
 
     def _extract_range(self, win_lo: int, win_hi: int) -> Optional[RecordBatch]:
         """Read cells in [win_lo, win_hi) without mutating the table."""
@@ -1196,6 +1262,14 @@ class WindowAggState:
             )
         self._outn_pin[0:1].copy_(self.out_n, non_blocking=True)
         self._outn_pin[1:2].copy_(self.error_flag, non_blocking=True)
+        if self.radix:
+            if self._spill_pin is None:
+                self._spill_pin = torch.zeros(
+                    1,
+                    dtype=torch.int64,
+                    pin_memory=torch.cuda.is_available(),
+                )
+            self._spill_pin.copy_(self.spill_total, non_blocking=True)
         self._close_ev = torch.cuda.Event()
         self._close_ev.record()
         self._close_pending = True
@@ -1215,6 +1289,8 @@ class WindowAggState:
             self._carry_cpu = None
             return out
         self._close_ev.synchronize()
+        if self.radix:
+            self._note_spill(int(self._spill_pin[0].item()))
         n = int(self._outn_pin[0].item())
         _check_error_flag(
             int(self._outn_pin[1].item()), "keyed window state table"
