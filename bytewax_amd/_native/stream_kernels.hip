@@ -3358,6 +3358,365 @@ __global__ void k_join_extract(
 }
 
 // ---------------------------------------------------------------------------
+// Windowed two-sided join ("first"/"last" insert, "final" emit).  The
+// table is the whole-table layout of the stats writers: `tkeys` holds
+// `window << 32 | key` (EMPTY_SLOT = empty), and per side there are a
+// timestamp array `tts` (the stamp: the timestamp of the event that
+// holds the side) and a value array `tval`.  A side is present iff its
+// stamp differs from WJ_TS_NONE<FIRST> (I64_MIN under "last", I64_MAX
+// under "first"); event timestamps lie strictly between the two, so a
+// value is never a sentinel.  `telect` is one int32 election word per
+// slot, shared by both sides because one insert call handles one side.
+//
+// Winner rule of one (key, window, side): "last" keeps the event with
+// the greatest (ts, arrival), "first" the one with the smallest, where
+// arrival orders batches by call and rows by index.
+//
+// Insert is three launches on one stream over one side's batch:
+//   stamp   find_slot, then atomicMax ("last") / atomicMin ("first")
+//           of ts on the side's stamp.  The slot goes to `ev_slot[i]`
+//           (-1: table full) so that the later passes do not probe.
+//           Under "first" an event that strictly lowers the stamp
+//           opens the cell's election word (WJ_IDLE -> WJ_OPEN).
+//   elect   every event whose ts equals the now final stamp bids its
+//           row index: atomicMax ("last") / atomicMin ("first") on the
+//           election word.  Under "first" only opened cells take bids.
+//   commit  the event whose row index equals the elected one stores
+//           its value and puts the election word back to idle.
+//
+// Exactness.  (1) Who may write a value: only the commit pass, and
+// there only the event whose row equals the cell's election word.  Row
+// indices are unique within a batch, so at most one event per cell and
+// batch stores; the word is idle between inserts, and idle (-1 under
+// "last", WJ_IDLE under "first") equals no row index, the launcher
+// bounds n below WJ_OPEN.  (2) That event is the winner.  After the
+// stamp pass a stamp is max ("last") / min ("first") of its old value
+// and the batch's timestamps for the cell, atomics being total per
+// address.  "last": a batch event wins iff its ts is >= every earlier
+// one's, i.e. equals the new stamp (an equal earlier batch loses to
+// the later arrival), and among those the greatest row wins: exactly
+// the bidders and the atomicMax of the elect pass.  If none equals the
+// stamp the earlier holder stays and nobody bids.  "first": a batch
+// event wins iff its ts is strictly below the old stamp (an equal
+// earlier batch keeps the side) and equals the new stamp, smallest row
+// first.  The stamp went strictly down iff some event's atomicMin
+// returned a value above its ts, and that event opened the word; so
+// "opened and ts == stamp" is exactly the winning set, and an event
+// that merely equals an earlier batch's stamp finds the word idle.
+// Every opened cell has a bidder (the event that set the final
+// stamp), so every opened word is put back by the commit.  (3) Launch
+// order is enough: each pass reads only what the pass before wrote
+// (stamps and ev_slot, then election words), and launches on one
+// stream run in order with their writes visible to the next.  Every
+// other writer of the table (close, resets, restore) is enqueued on
+// that stream too.
+#define WJ_IDLE 0x7FFFFFFF  // "first": no election open
+#define WJ_OPEN 0x7FFFFFFE  // "first": stamp lowered, bids welcome
+
+template <bool FIRST>
+__device__ __forceinline__ constexpr long long wj_ts_none() {
+  return FIRST ? INT64_MAX : INT64_MIN;
+}
+
+template <bool FIRST, typename TS = int64_t>
+__global__ void k_wjoin_stamp(
+    const int32_t* __restrict__ keys,
+    const TS* __restrict__ ts,
+    int64_t n,
+    uint64_t* __restrict__ tkeys,
+    long long* __restrict__ tts,  // this side's stamps
+    int* __restrict__ telect,
+    uint64_t mask,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    int32_t* __restrict__ ev_slot,
+    unsigned long long* __restrict__ max_ts,
+    int* __restrict__ error_flag) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  int64_t local_max = 0;
+  for (; i < n; i += stride) {
+    int64_t t = (int64_t)ts[i] + ts_base;
+    if (t > local_max) local_max = t;
+    int64_t win = floor_div(t - align_ms, len_ms);
+    uint64_t packed =
+        ((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)keys[i];
+    uint64_t slot = find_slot(tkeys, mask, packed);
+    if (slot == ~0ULL) {
+      atomicOr(error_flag, 1);
+      ev_slot[i] = -1;
+      continue;
+    }
+    ev_slot[i] = (int32_t)slot;
+    if constexpr (FIRST) {
+      long long old = atomicMin(&tts[slot], (long long)t);
+      if ((long long)t < old) atomicMin(&telect[slot], WJ_OPEN);
+    } else {
+      atomicMax(&tts[slot], (long long)t);
+    }
+  }
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    int64_t other = __shfl_down((long long)local_max, off);
+    if (other > local_max) local_max = other;
+  }
+  if ((threadIdx.x & (WAVE - 1)) == 0 && local_max > 0) {
+    atomicMax(max_ts, (unsigned long long)local_max);
+  }
+}
+
+template <bool FIRST, typename TS = int64_t>
+__global__ void k_wjoin_elect(
+    const TS* __restrict__ ts,
+    int64_t n,
+    int64_t ts_base,
+    const long long* __restrict__ tts,
+    int* __restrict__ telect,
+    const int32_t* __restrict__ ev_slot) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (; i < n; i += stride) {
+    int32_t slot = ev_slot[i];
+    if (slot < 0) continue;
+    if ((long long)((int64_t)ts[i] + ts_base) != tts[slot]) continue;
+    if constexpr (FIRST) {
+      // Bids only lower an opened word, so it never reads idle again
+      // within this pass.
+      if (telect[slot] != WJ_IDLE) atomicMin(&telect[slot], (int)i);
+    } else {
+      atomicMax(&telect[slot], (int)i);
+    }
+  }
+}
+
+template <bool FIRST>
+__global__ void k_wjoin_commit(
+    const int64_t* __restrict__ vals,
+    int64_t n,
+    long long* __restrict__ tval,  // this side's values
+    int* __restrict__ telect,
+    const int32_t* __restrict__ ev_slot) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (; i < n; i += stride) {
+    int32_t slot = ev_slot[i];
+    if (slot < 0) continue;
+    // The elected row is the only one that can compare equal: the
+    // other events of the cell see either it or the idle value.
+    if (telect[slot] != (int)i) continue;
+    tval[slot] = vals[i];
+    telect[slot] = FIRST ? WJ_IDLE : -1;
+  }
+}
+
+// Presence mask of a cell from its two stamps (bit s = side s).
+__device__ __forceinline__ int wj_mask(
+    long long t0, long long t1, long long ts_none) {
+  return (t0 != ts_none ? 1 : 0) | (t1 != ts_none ? 2 : 0);
+}
+
+// Windowed-join close with reclamation: the join's twin of
+// k_stats_close_migrate.  One pass over the table in CM_CHUNK-slot
+// chunks sorts every cell by its window id `w`:
+//   win_lo <= w < win_hi  emit keys, wins, v0, v1, mask;
+//   w >= win_hi           migrate into the fresh table, both stamps
+//                         and both values;
+//   w < win_lo            drop.  Such a cell was made by an event
+//                         behind the closed horizon (there is no late
+//                         tracking); its window has been emitted and
+//                         no extract reads it.
+// The caller swaps the tables afterwards and resets the retired one
+// (keys EMPTY, stamps `ts_none`, values 0, election words idle).
+// Election words are idle between inserts, so they are not migrated:
+// the fresh table's are idle already.
+//
+// Keys are loaded 16 bytes per lane and stay in registers; stamps and
+// values are read only for a slot that is emitted or migrated, at the
+// point where it is.  Output rows are reserved per chunk as in
+// k_close_migrate: wave scan, cross-wave LDS step, one
+// `atomicAdd(out_n, chunk_total)` by thread 0; rows past `cap` are
+// counted, not written.  A missing side's value column reads 0; the
+// mask, never the value, says whether a side is there.
+//
+// Exactness is k_stats_close_migrate's: (1) the target is fresh and
+// every migrated cell is unique, so exactly one thread claims a given
+// slot and stores its four words plainly; (2) nothing else writes
+// either table meanwhile: the insert passes, the resets and this
+// kernel are all enqueued on one stream.
+__global__ __launch_bounds__(CM_BLK) void k_wjoin_close_migrate(
+    const uint64_t* __restrict__ tkeys,
+    const long long* __restrict__ tts0,
+    const long long* __restrict__ tts1,
+    const long long* __restrict__ tv0,
+    const long long* __restrict__ tv1,
+    int64_t nslots,
+    int64_t win_lo,
+    int64_t win_hi,
+    long long ts_none,
+    uint64_t* __restrict__ nkeys,
+    long long* __restrict__ nts0,
+    long long* __restrict__ nts1,
+    long long* __restrict__ nv0,
+    long long* __restrict__ nv1,
+    uint64_t mask,
+    int32_t* __restrict__ out_keys,
+    int32_t* __restrict__ out_wins,
+    int64_t* __restrict__ out_v0,
+    int64_t* __restrict__ out_v1,
+    int32_t* __restrict__ out_mask,
+    int* __restrict__ out_n,
+    int64_t cap,
+    int* __restrict__ error_flag) {
+  constexpr int NW = CM_BLK / WAVE;
+  // Double-buffered by chunk parity: two barriers per chunk suffice.
+  __shared__ int s_wave[2][NW];
+  __shared__ int s_base[2];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const bool vec = (((uintptr_t)tkeys) & 15) == 0;
+  const int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  int par = 0;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x, par ^= 1) {
+    // Slot of k[q]: s0 + (q / 2) * (CM_BLK * 2) + (q & 1).
+    const int64_t s0 = c * CM_CHUNK + threadIdx.x * 2;
+    uint64_t k[CM_PER];
+    for (int j = 0; j < CM_PER / 2; ++j) {
+      int64_t s = s0 + (int64_t)j * (CM_BLK * 2);
+      if (vec && s + 1 < nslots) {
+        ulonglong2 kk = *(const ulonglong2*)(tkeys + s);
+        k[2 * j] = kk.x;
+        k[2 * j + 1] = kk.y;
+      } else {
+        for (int q = 0; q < 2; ++q) {
+          k[2 * j + q] = s + q < nslots ? tkeys[s + q] : EMPTY_SLOT;
+        }
+      }
+    }
+    unsigned takem = 0;
+    for (int q = 0; q < CM_PER; ++q) {
+      if (k[q] == EMPTY_SLOT) continue;
+      int64_t win = (int64_t)(int32_t)(uint32_t)(k[q] >> 32);
+      if (win < win_lo) continue;
+      int64_t s = s0 + (int64_t)(q >> 1) * (CM_BLK * 2) + (q & 1);
+      if (win < win_hi) {
+        // A cell with no side (only a timestamp equal to `ts_none`,
+        // outside the documented range, leaves one) is not a row.
+        if (wj_mask(tts0[s], tts1[s], ts_none) != 0) takem |= 1u << q;
+      } else {
+        long long a0 = tts0[s], a1 = tts1[s], b0 = tv0[s], b1 = tv1[s];
+        uint64_t slot = find_slot(nkeys, mask, k[q]);
+        if (slot == ~0ULL) {
+          atomicOr(error_flag, 1);
+        } else {
+          nts0[slot] = a0;
+          nts1[slot] = a1;
+          nv0[slot] = b0;
+          nv1[slot] = b1;
+        }
+      }
+    }
+    const int cnt = __popc(takem);
+    int incl = cnt;
+    for (int off = 1; off < WAVE; off <<= 1) {
+      int o = __shfl_up(incl, off);
+      if (lane >= off) incl += o;
+    }
+    if (lane == WAVE - 1) s_wave[par][wave] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int total = 0;
+      for (int w = 0; w < NW; ++w) total += s_wave[par][w];
+      s_base[par] = total > 0 ? atomicAdd(out_n, total) : 0;
+    }
+    __syncthreads();
+    if (takem != 0) {
+      int64_t idx = (int64_t)s_base[par] + (incl - cnt);
+      for (int w = 0; w < wave; ++w) idx += s_wave[par][w];
+      for (int q = 0; q < CM_PER; ++q) {
+        if (!((takem >> q) & 1u)) continue;
+        if (idx < cap) {
+          int64_t s = s0 + (int64_t)(q >> 1) * (CM_BLK * 2) + (q & 1);
+          int m = wj_mask(tts0[s], tts1[s], ts_none);
+          out_keys[idx] = (int32_t)(uint32_t)(k[q] & 0xFFFFFFFFULL);
+          out_wins[idx] = (int32_t)(uint32_t)(k[q] >> 32);
+          out_v0[idx] = (m & 1) ? tv0[s] : 0;
+          out_v1[idx] = (m & 2) ? tv1[s] : 0;
+          out_mask[idx] = m;
+        }
+        ++idx;
+      }
+    }
+  }
+}
+
+// Non-mutating scan of the windowed-join table (snapshots, EOF): every
+// live cell of windows in [win_lo, win_hi) with both values, both
+// stamps and the presence mask (a missing side's value and stamp read
+// 0).  Rows are reserved per wave.
+__global__ void k_wjoin_extract(
+    const uint64_t* __restrict__ tkeys,
+    const long long* __restrict__ tts0,
+    const long long* __restrict__ tts1,
+    const long long* __restrict__ tv0,
+    const long long* __restrict__ tv1,
+    int64_t nslots,
+    int64_t win_lo,
+    int64_t win_hi,
+    long long ts_none,
+    int32_t* __restrict__ out_keys,
+    int32_t* __restrict__ out_wins,
+    int64_t* __restrict__ out_v0,
+    int64_t* __restrict__ out_v1,
+    int64_t* __restrict__ out_t0,
+    int64_t* __restrict__ out_t1,
+    int32_t* __restrict__ out_mask,
+    int* __restrict__ out_n,
+    int64_t cap) {
+  // Whole waves stay in the loop together: the ballot below needs
+  // every lane of a wave that has any slot left.
+  int64_t base_i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  int lane = threadIdx.x & (WAVE - 1);
+  for (int64_t i = base_i; i - lane < nslots; i += stride) {
+    uint64_t k = i < nslots ? tkeys[i] : EMPTY_SLOT;
+    bool take = false;
+    int32_t win = 0;
+    int m = 0;
+    long long a0 = 0, a1 = 0;
+    if (k != EMPTY_SLOT) {
+      win = (int32_t)(uint32_t)(k >> 32);
+      if ((int64_t)win >= win_lo && (int64_t)win < win_hi) {
+        a0 = tts0[i];
+        a1 = tts1[i];
+        m = wj_mask(a0, a1, ts_none);
+        take = m != 0;
+      }
+    }
+    unsigned long long ball = __ballot(take);
+    if (ball != 0) {
+      int wave_total = __popcll(ball);
+      int rank = __popcll(ball & ((1ULL << lane) - 1ULL));
+      int base = 0;
+      int lead = __ffsll((unsigned long long)ball) - 1;
+      if (lane == lead) base = atomicAdd(out_n, wave_total);
+      base = __shfl(base, lead);
+      if (take) {
+        int64_t idx = base + rank;
+        if (idx < cap) {
+          out_keys[idx] = (int32_t)(uint32_t)(k & 0xFFFFFFFFULL);
+          out_wins[idx] = win;
+          out_v0[idx] = (m & 1) ? tv0[i] : 0;
+          out_v1[idx] = (m & 2) ? tv1[i] : 0;
+          out_t0[idx] = (m & 1) ? a0 : 0;
+          out_t1[idx] = (m & 2) ? a1 : 0;
+          out_mask[idx] = m;
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Session windows (gap-based).  Per-key state is one table cell:
 // (session_start, last_ts, accumulator).  Batches arrive SORTED by
 // (key, ts) — the host wrapper sorts — and one thread walks each
@@ -6835,6 +7194,217 @@ void join_extract(
       out_n.data_ptr<int32_t>(), out_keys.numel());
 }
 
+// One side's batch into the windowed-join table: the stamp, elect and
+// commit launches of k_wjoin_stamp on the current stream.  `tts` and
+// `tval` are the side's arrays, `ev_slot` a scratch of at least n
+// int32.  `ts` is absolute int64 or int32 deltas against `ts_base`.
+void wjoin_insert(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    torch::Tensor vals,
+    torch::Tensor tkeys,
+    torch::Tensor tts,
+    torch::Tensor tval,
+    torch::Tensor telect,
+    torch::Tensor ev_slot,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    bool first) {
+  check_dev(keys, torch::kInt32, "keys");
+  check_dev(vals, torch::kInt64, "vals");
+  check_dev(tkeys, torch::kInt64, "tkeys");
+  check_dev(tts, torch::kInt64, "tts");
+  check_dev(tval, torch::kInt64, "tval");
+  check_dev(telect, torch::kInt32, "telect");
+  check_dev(ev_slot, torch::kInt32, "ev_slot");
+  check_dev(max_ts, torch::kInt64, "max_ts");
+  check_dev(error_flag, torch::kInt32, "error_flag");
+  const bool ts32 = ts.scalar_type() == torch::kInt32;
+  check_dev(ts, ts32 ? torch::kInt32 : torch::kInt64, "ts");
+  int64_t n = keys.numel();
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK(nslots > 0 && (nslots & (nslots - 1)) == 0,
+              "table size must be a power of two");
+  // ev_slot holds slot indices as int32.
+  TORCH_CHECK(nslots <= (int64_t)1 << 30, "table too large");
+  TORCH_CHECK(tts.numel() == nslots && tval.numel() == nslots &&
+                  telect.numel() == nslots,
+              "table size mismatch");
+  TORCH_CHECK(ts.numel() == n && vals.numel() == n, "column size mismatch");
+  TORCH_CHECK(ev_slot.numel() >= n, "ev_slot too small");
+  // Row indices are bid as int32 below the election sentinels.
+  TORCH_CHECK(n < (int64_t)WJ_OPEN, "batch too large");
+  TORCH_CHECK(len_ms > 0, "window length must be positive");
+  TORCH_CHECK(max_ts.numel() >= 1 && error_flag.numel() >= 1,
+              "max_ts and error_flag must hold one element");
+  if (n == 0) return;
+  auto stream = at::hip::getCurrentHIPStream();
+  dim3 block(256);
+  dim3 grid(n_blocks(n, 256));
+  auto run = [&](auto first_c, auto* tsp) {
+    constexpr bool F = decltype(first_c)::value;
+    using TSV = std::remove_cv_t<std::remove_pointer_t<decltype(tsp)>>;
+    hipLaunchKernelGGL(
+        (k_wjoin_stamp<F, TSV>), grid, block, 0, stream,
+        keys.data_ptr<int32_t>(), tsp, n,
+        (uint64_t*)tkeys.data_ptr<int64_t>(),
+        (long long*)tts.data_ptr<int64_t>(), telect.data_ptr<int32_t>(),
+        (uint64_t)(nslots - 1), align_ms, len_ms, ts_base,
+        ev_slot.data_ptr<int32_t>(),
+        (unsigned long long*)max_ts.data_ptr<int64_t>(),
+        error_flag.data_ptr<int32_t>());
+    hipLaunchKernelGGL(
+        (k_wjoin_elect<F, TSV>), grid, block, 0, stream, tsp, n, ts_base,
+        (const long long*)tts.data_ptr<int64_t>(),
+        telect.data_ptr<int32_t>(),
+        (const int32_t*)ev_slot.data_ptr<int32_t>());
+    hipLaunchKernelGGL(
+        (k_wjoin_commit<F>), grid, block, 0, stream,
+        (const int64_t*)vals.data_ptr<int64_t>(), n,
+        (long long*)tval.data_ptr<int64_t>(), telect.data_ptr<int32_t>(),
+        (const int32_t*)ev_slot.data_ptr<int32_t>());
+  };
+  auto by_ts = [&](auto first_c) {
+    if (ts32)
+      run(first_c, (const int32_t*)ts.data_ptr<int32_t>());
+    else
+      run(first_c, (const int64_t*)ts.data_ptr<int64_t>());
+  };
+  if (first)
+    by_ts(std::true_type{});
+  else
+    by_ts(std::false_type{});
+}
+
+static void check_wjoin_table(
+    const torch::Tensor& tkeys, const torch::Tensor* const* cols, int ncols) {
+  check_dev(tkeys, torch::kInt64, "tkeys");
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK(nslots > 0 && (nslots & (nslots - 1)) == 0,
+              "table size must be a power of two");
+  for (int i = 0; i < ncols; ++i) {
+    check_dev(*cols[i], torch::kInt64, "window join table array");
+    TORCH_CHECK(cols[i]->numel() == nslots, "table size mismatch");
+  }
+}
+
+// Windowed-join close with reclamation (see k_wjoin_close_migrate);
+// the launch shape of stats_close_migrate.  `ts_none` is the stamp of
+// an absent side.
+void wjoin_close_migrate(
+    torch::Tensor tkeys,
+    torch::Tensor tts0,
+    torch::Tensor tts1,
+    torch::Tensor tv0,
+    torch::Tensor tv1,
+    torch::Tensor nkeys,
+    torch::Tensor nts0,
+    torch::Tensor nts1,
+    torch::Tensor nv0,
+    torch::Tensor nv1,
+    int64_t win_lo,
+    int64_t win_hi,
+    int64_t ts_none,
+    torch::Tensor out_keys,
+    torch::Tensor out_wins,
+    torch::Tensor out_v0,
+    torch::Tensor out_v1,
+    torch::Tensor out_mask,
+    torch::Tensor out_n,
+    torch::Tensor error_flag) {
+  const torch::Tensor* live[] = {&tts0, &tts1, &tv0, &tv1};
+  const torch::Tensor* fresh[] = {&nts0, &nts1, &nv0, &nv1};
+  check_wjoin_table(tkeys, live, 4);
+  check_wjoin_table(nkeys, fresh, 4);
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK(nkeys.numel() == nslots, "table size mismatch");
+  check_dev(out_keys, torch::kInt32, "out_keys");
+  check_dev(out_wins, torch::kInt32, "out_wins");
+  check_dev(out_mask, torch::kInt32, "out_mask");
+  check_dev(out_v0, torch::kInt64, "out_v0");
+  check_dev(out_v1, torch::kInt64, "out_v1");
+  check_dev(out_n, torch::kInt32, "out_n");
+  check_dev(error_flag, torch::kInt32, "error_flag");
+  TORCH_CHECK(out_n.numel() >= 1 && error_flag.numel() >= 1,
+              "out_n and error_flag must hold one element");
+  int64_t cap = out_keys.numel();
+  TORCH_CHECK(out_wins.numel() == cap && out_mask.numel() == cap &&
+                  out_v0.numel() == cap && out_v1.numel() == cap,
+              "output size mismatch");
+  int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  unsigned grid = (unsigned)(nchunks < CM_MAX_GRID ? nchunks : CM_MAX_GRID);
+  hipLaunchKernelGGL(
+      k_wjoin_close_migrate, dim3(grid), dim3(CM_BLK), 0,
+      at::hip::getCurrentHIPStream(),
+      (const uint64_t*)tkeys.data_ptr<int64_t>(),
+      (const long long*)tts0.data_ptr<int64_t>(),
+      (const long long*)tts1.data_ptr<int64_t>(),
+      (const long long*)tv0.data_ptr<int64_t>(),
+      (const long long*)tv1.data_ptr<int64_t>(), nslots, win_lo, win_hi,
+      (long long)ts_none, (uint64_t*)nkeys.data_ptr<int64_t>(),
+      (long long*)nts0.data_ptr<int64_t>(),
+      (long long*)nts1.data_ptr<int64_t>(),
+      (long long*)nv0.data_ptr<int64_t>(),
+      (long long*)nv1.data_ptr<int64_t>(), (uint64_t)(nslots - 1),
+      out_keys.data_ptr<int32_t>(), out_wins.data_ptr<int32_t>(),
+      out_v0.data_ptr<int64_t>(), out_v1.data_ptr<int64_t>(),
+      out_mask.data_ptr<int32_t>(), out_n.data_ptr<int32_t>(), cap,
+      error_flag.data_ptr<int32_t>());
+}
+
+// Non-mutating extract of the windowed-join cells in [win_lo, win_hi)
+// (see k_wjoin_extract).
+void wjoin_extract(
+    torch::Tensor tkeys,
+    torch::Tensor tts0,
+    torch::Tensor tts1,
+    torch::Tensor tv0,
+    torch::Tensor tv1,
+    int64_t win_lo,
+    int64_t win_hi,
+    int64_t ts_none,
+    torch::Tensor out_keys,
+    torch::Tensor out_wins,
+    torch::Tensor out_v0,
+    torch::Tensor out_v1,
+    torch::Tensor out_t0,
+    torch::Tensor out_t1,
+    torch::Tensor out_mask,
+    torch::Tensor out_n) {
+  const torch::Tensor* live[] = {&tts0, &tts1, &tv0, &tv1};
+  check_wjoin_table(tkeys, live, 4);
+  int64_t nslots = tkeys.numel();
+  check_dev(out_keys, torch::kInt32, "out_keys");
+  check_dev(out_wins, torch::kInt32, "out_wins");
+  check_dev(out_mask, torch::kInt32, "out_mask");
+  check_dev(out_n, torch::kInt32, "out_n");
+  TORCH_CHECK(out_n.numel() >= 1, "out_n must hold one element");
+  int64_t cap = out_keys.numel();
+  TORCH_CHECK(out_wins.numel() == cap && out_mask.numel() == cap,
+              "output size mismatch");
+  const torch::Tensor* outs[] = {&out_v0, &out_v1, &out_t0, &out_t1};
+  for (const torch::Tensor* t : outs) {
+    check_dev(*t, torch::kInt64, "window join output column");
+    TORCH_CHECK(t->numel() == cap, "output size mismatch");
+  }
+  hipLaunchKernelGGL(
+      k_wjoin_extract, dim3(n_blocks(nslots, 256)), dim3(256), 0,
+      at::hip::getCurrentHIPStream(),
+      (const uint64_t*)tkeys.data_ptr<int64_t>(),
+      (const long long*)tts0.data_ptr<int64_t>(),
+      (const long long*)tts1.data_ptr<int64_t>(),
+      (const long long*)tv0.data_ptr<int64_t>(),
+      (const long long*)tv1.data_ptr<int64_t>(), nslots, win_lo, win_hi,
+      (long long)ts_none, out_keys.data_ptr<int32_t>(),
+      out_wins.data_ptr<int32_t>(), out_v0.data_ptr<int64_t>(),
+      out_v1.data_ptr<int64_t>(), out_t0.data_ptr<int64_t>(),
+      out_t1.data_ptr<int64_t>(), out_mask.data_ptr<int32_t>(),
+      out_n.data_ptr<int32_t>(), cap);
+}
+
 int64_t filter_compact(
     torch::Tensor keys,
     torch::Tensor ts,
@@ -7751,6 +8321,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "the session table (gap >= batch span fast path)");
   m.def("join_extract", &join_extract,
         "Extract live join state (recovery snapshot)");
+  m.def("wjoin_insert", &wjoin_insert,
+        "Windowed join: insert one side's batch (stamp, elect, commit)");
+  m.def("wjoin_close_migrate", &wjoin_close_migrate,
+        "Windowed join close: emit [win_lo, win_hi), migrate the cells "
+        "at or above win_hi");
+  m.def("wjoin_extract", &wjoin_extract,
+        "Windowed join: extract live cells with stamps (non-mutating)");
   m.def("filter_compact", &filter_compact,
         "Stream compaction of a RecordBatch by a boolean mask");
   m.def("bucket_hist", &bucket_hist, "Per-destination counts for exchange");

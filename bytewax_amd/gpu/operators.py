@@ -40,6 +40,7 @@ __all__ = [
     "keyed_window_agg",
     "keyed_window_agg_str",
     "stream_join",
+    "window_join",
 ]
 
 
@@ -1144,6 +1145,160 @@ def stream_join(
         if dist.is_available() and dist.is_initialized()
         else "shard-0"
     )
+    l_labeled = op.map("wrap_l", left, lambda b: (shard, (0, b)))
+    r_labeled = op.map("wrap_r", right, lambda b: (shard, (1, b)))
+    merged = op.merge("merge", l_labeled, r_labeled)
+    joined = op.stateful_batch("join", merged, shim_builder)
+    return op.map("unwrap", joined, lambda kv: kv[1])
+
+
+class _DeviceWindowJoinLogic(StatefulBatchLogic):
+    """Holds the HBM windowed-join table; values are (side,
+    RecordBatch)."""
+
+    def __init__(self, state, wait_ms: int, resume=None):
+        self.state = state
+        self.wait_ms = wait_ms
+        if resume is not None:
+            resume = dict(resume)
+            world = resume.pop("__world__", 1)
+            if world != 1:
+                msg = (
+                    f"window join snapshot of {world} workers cannot be "
+                    "restored on one: the windowed join is single-GPU and "
+                    "does not rescale"
+                )
+                raise ValueError(msg)
+            self.state.restore_from_host(resume)
+
+    def on_batch(self, side_batches):
+        for side, batch in side_batches:
+            self.state.insert(side, batch)
+        # Reclaiming close: the table keeps only the open windows.
+        closed = self.state.close_below(
+            self.state.horizon_for(self.state.max_ts_host, self.wait_ms)
+        )
+        out = [] if closed is None else [closed]
+        return (out, StatefulBatchLogic.RETAIN)
+
+    def on_eof(self):
+        closed = self.state.close_eof()
+        out = [] if closed is None else [closed]
+        return (out, StatefulBatchLogic.RETAIN)
+
+    def snapshot(self):
+        snap = dict(self.state.snapshot_to_host())
+        snap["__world__"] = 1
+        return snap
+
+
+@operator
+def window_join(
+    step_id: str,
+    left: Stream[RecordBatch],
+    right: Stream[RecordBatch],
+    align_to: datetime,
+    length: timedelta,
+    wait: timedelta = timedelta(0),
+    insert_mode: str = "last",
+    emit_mode: str = "final",
+    slots_pow: int = 20,
+    out_cap: int = 1 << 20,
+    device: str = "cuda",
+    exchange: Optional[bool] = None,
+) -> Stream[Dict[str, Any]]:
+    """Two-sided join over tumbling event-time windows of columnar
+    batches on GPU ("first" or "last" insert, "final" emit): the device
+    counterpart of `join_window` with an `EventClock`, a
+    `TumblingWindower` and ``ordered=True``.
+
+    An event ``(key, ts, val)`` of either side belongs to window
+    ``(ts - align_to) // length``, and each (key, window) keeps one
+    value per side.  With ``insert_mode="last"`` that is the value of
+    the event with the greatest timestamp; among equal timestamps the
+    latest arrival wins (a later batch beats an earlier one, within a
+    batch the greater row index).  With ``"first"`` it is the smallest
+    timestamp, and among equals the earliest arrival.  Both are what a
+    stable sort by timestamp followed by the host's `on_value` gives,
+    exactly and reproducibly, duplicates within a batch included.
+
+    Once the watermark minus `wait` passes a window's end, every cell
+    of that window with at least one side is emitted once, as a dict
+    of columnar device tensors {keys, wins, v0, v1, mask}: ``mask`` bit
+    0 says the left side is present, bit 1 the right; a missing side's
+    value column reads 0 (values are arbitrary int64, so only the mask
+    tells).  At EOF every remaining cell is emitted.
+
+    A window close reclaims the closed cells, so the stream may run
+    unbounded: size `slots_pow` (2^slots_pow table slots, best kept
+    under half full) for the (key, window) cells of the windows that
+    are open at one time, not for every cell the stream will produce.
+
+    Ingestion must be watermark-ordered across batches (each batch's
+    events at or after the watermark set by the earlier ones of either
+    side, minus `wait`): this operator does not track late events, and
+    nothing checks the ordering — an event behind the watermark makes
+    a cell in a window that has already been emitted, and the next
+    close drops it.  No event may lie before `align_to` (window -1 of
+    key -1 would pack to the table's empty-slot sentinel), timestamps
+    lie strictly inside the int64 range and window ids within int32.
+
+    Raises `ValueError` at build time for an `emit_mode` other than
+    ``"final"`` ("complete" and "running" depend on the order of single
+    events across the sides) and for an `insert_mode` other than
+    ``"first"`` or ``"last"`` ("product" included); only two sides and
+    tumbling windows exist here.  Raises `NotImplementedError` for
+    ``exchange=True`` or a process group of more than one rank.
+    Raises `RuntimeError` when the table overflows or one close has
+    more than `out_cap` rows; neither ever returns short output.
+    """
+    import torch
+    import torch.distributed as dist
+
+    from .state import WindowJoinState
+    from . import _ms as to_ms
+
+    if emit_mode != "final":
+        msg = (
+            f"window_join emit mode {emit_mode!r} is not supported on the "
+            "device path: only 'final' is"
+        )
+        raise ValueError(msg)
+    if insert_mode not in ("first", "last"):
+        msg = (
+            f"window_join insert mode {insert_mode!r} is not supported on "
+            "the device path: use 'first' or 'last'"
+        )
+        raise ValueError(msg)
+    world = (
+        dist.get_world_size()
+        if dist.is_available() and dist.is_initialized()
+        else 1
+    )
+    if exchange or world > 1:
+        msg = (
+            "window_join is single-GPU: a multi-GPU windowed join needs the "
+            "two sides' collectives ordered identically on every rank, "
+            "which this operator does not do yet"
+        )
+        raise NotImplementedError(msg)
+
+    align_ms = to_ms(align_to)
+    len_ms = int(length.total_seconds() * 1000)
+    wait_ms = int(wait.total_seconds() * 1000)
+    if len_ms <= 0:
+        msg = "window_join length must be positive"
+        raise ValueError(msg)
+
+    def shim_builder(resume_state):
+        state = WindowJoinState(
+            torch.device(device), align_ms, len_ms,
+            insert_mode=insert_mode, slots_pow=slots_pow,
+            out_cap=out_cap, wait_ms=wait_ms,
+        )
+        return _DeviceWindowJoinLogic(state, wait_ms, resume_state)
+
+    shard = "shard-0"
     l_labeled = op.map("wrap_l", left, lambda b: (shard, (0, b)))
     r_labeled = op.map("wrap_r", right, lambda b: (shard, (1, b)))
     merged = op.merge("merge", l_labeled, r_labeled)

@@ -6,9 +6,12 @@ Device twins of `reduce_final`-style keyed aggregations and the
 - :class:`StatsAggState` — 1BRC-style count/sum/min/max per
   (key, window) in one fused pass (BASELINE config 5);
 - :class:`HashJoinState` — stream-stream join with HBM-resident
-  open-address state, "last" insert / "complete" emit (config 4).
+  open-address state, "last" insert / "complete" emit (config 4);
+- :class:`WindowJoinState` — the same join per tumbling event-time
+  window, "first" or "last" insert / "final" emit, with a close that
+  reclaims the closed cells.
 
-Both support pinned-host snapshot spill for recovery and have CPU
+All support pinned-host snapshot spill for recovery and have CPU
 twins for GPU-less test runs.
 """
 
@@ -1198,6 +1201,411 @@ class HashJoinState:
         )
         self.out_n.zero_()
         return out
+
+
+_WJOIN_COLS = ("keys", "wins", "v0", "v1", "mask")
+_WJOIN_MODES = ("first", "last")
+
+
+def _wjoin_rows(hit) -> Optional[Dict[str, Any]]:
+    """The five-column dict of a list of (key, win, [t0, v0, t1, v1])
+    cells, None standing for an absent side."""
+    import torch
+
+    if not hit:
+        return None
+    return {
+        "keys": torch.tensor([k for k, _w, _c in hit], dtype=torch.int32),
+        "wins": torch.tensor([w for _k, w, _c in hit], dtype=torch.int32),
+        "v0": torch.tensor(
+            [0 if c[0] is None else c[1] for *_x, c in hit], dtype=torch.int64
+        ),
+        "v1": torch.tensor(
+            [0 if c[2] is None else c[3] for *_x, c in hit], dtype=torch.int64
+        ),
+        "mask": torch.tensor(
+            [
+                (c[0] is not None) | ((c[2] is not None) << 1)
+                for *_x, c in hit
+            ],
+            dtype=torch.int32,
+        ),
+    }
+
+
+class WindowJoinState:
+    """Two-sided join over tumbling event-time windows on device:
+    "first" or "last" insert, "final" emit (the device twin of the
+    host `join_window` with an `EventClock`, a `TumblingWindower` and
+    ``ordered=True``).
+
+    One cell per (key, window) holds, per side, a value and the
+    timestamp of the event that won it.  Under "last" the event with
+    the greatest timestamp holds a side, and among equal timestamps
+    the latest arrival (a later batch beats an earlier one, within a
+    batch the greater row index); under "first" the smallest timestamp
+    and the earliest arrival.  That is what a stable sort by timestamp
+    followed by the host's `on_value` gives, and it is exact for every
+    input, run after run.
+
+    A close emits each cell of a due window once, as columns `keys`,
+    `wins`, `v0`, `v1` and `mask` (bit ``s`` set: side ``s`` present; a
+    missing side's value column reads 0), and reclaims its slot.
+    Values are arbitrary int64; timestamps lie strictly inside the
+    int64 range.  There is no late tracking: see `window_join` for the
+    ordering contract.
+    """
+
+    def __init__(
+        self,
+        device,
+        align_ms: int,
+        len_ms: int,
+        insert_mode: str = "last",
+        slots_pow: int = 20,
+        out_cap: int = 1 << 20,
+        wait_ms: int = 0,
+    ):
+        import torch
+
+        if insert_mode not in _WJOIN_MODES:
+            msg = (
+                f"window join insert mode {insert_mode!r} is not "
+                "supported on the device path: use 'first' or 'last'"
+            )
+            raise ValueError(msg)
+        if len_ms <= 0:
+            msg = "window length must be positive"
+            raise ValueError(msg)
+        self.device = device
+        self.align_ms = align_ms
+        self.len_ms = len_ms
+        self.insert_mode = insert_mode
+        self.first = insert_mode == "first"
+        self.wait_ms = wait_ms
+        self.max_ts_host = 0
+        self.closed_horizon = -(1 << 62)
+        #: The second table (keys, ts0, ts1, v0, v1, elect) that a
+        #: reclaiming close rebuilds the live cells into.  None until
+        #: a close has rows to emit.
+        self.tables_alt: Optional[Tuple[Any, ...]] = None
+        self.cpu = device.type == "cpu"
+        if self.cpu:
+            #: (key, win) -> [ts0, v0, ts1, v1]; None = side absent.
+            self._table: Dict[Tuple[int, int], List[Optional[int]]] = {}
+            return
+        self.k = ext()
+        self.nslots = 1 << slots_pow
+        #: Stamp of an absent side and idle election word (see
+        #: k_wjoin_stamp).
+        self.ts_none = _I64_MAX if self.first else _I64_MIN
+        self._fills = (
+            -1, self.ts_none, self.ts_none, 0, 0,
+            0x7FFFFFFF if self.first else -1,
+        )
+        (
+            self.tkeys, self.tts0, self.tts1, self.tv0, self.tv1,
+            self.telect,
+        ) = self._new_table()
+        self.ev_slot = torch.empty(0, dtype=torch.int32, device=device)
+        self.max_ts_dev = torch.zeros(1, dtype=torch.int64, device=device)
+        self.error_flag = torch.zeros(1, dtype=torch.int32, device=device)
+        self.out_cap = out_cap
+        self.out = {
+            name: torch.empty(
+                out_cap,
+                dtype=torch.int64 if name[0] in "vt" else torch.int32,
+                device=device,
+            )
+            for name in ("keys", "wins", "v0", "v1", "t0", "t1", "mask")
+        }
+        self.out_n = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def _new_table(self) -> Tuple[Any, ...]:
+        import torch
+
+        return tuple(
+            torch.full(
+                (self.nslots,),
+                fill,
+                dtype=torch.int32 if i == 5 else torch.int64,
+                device=self.device,
+            )
+            for i, fill in enumerate(self._fills)
+        )
+
+    def insert(self, side: int, batch: RecordBatch) -> None:
+        """Insert one side's batch (`side` 0 = left, 1 = right)."""
+        import torch
+
+        if side not in (0, 1):
+            msg = f"window join side must be 0 or 1, not {side!r}"
+            raise ValueError(msg)
+        if batch.vals is None:
+            msg = "window join requires a `vals` column"
+            raise ValueError(msg)
+        n = len(batch)
+        if self.cpu:
+            self._insert_cpu(side, batch)
+            return
+        if n:
+            if self.ev_slot.numel() < n:
+                self.ev_slot = torch.empty(
+                    n * 5 // 4, dtype=torch.int32, device=self.device
+                )
+            self.k.wjoin_insert(
+                batch.keys,
+                batch.ts,
+                batch.vals,
+                self.tkeys,
+                self.tts1 if side else self.tts0,
+                self.tv1 if side else self.tv0,
+                self.telect,
+                self.ev_slot,
+                self.max_ts_dev,
+                self.error_flag,
+                self.align_ms,
+                self.len_ms,
+                batch.ts_base,
+                self.first,
+            )
+        if batch.max_ts is not None:
+            if batch.max_ts > self.max_ts_host:
+                self.max_ts_host = batch.max_ts
+        elif n:
+            # No host-side hint: the watermark has to come back from
+            # the device.
+            dev_max = int(self.max_ts_dev.item())
+            if dev_max > self.max_ts_host:
+                self.max_ts_host = dev_max
+
+    def _insert_cpu(self, side: int, batch: RecordBatch) -> None:
+        import torch
+
+        keys = batch.keys.tolist()
+        ts = (batch.ts.to(torch.int64) + batch.ts_base).tolist()
+        vals = batch.vals.tolist()
+        # Rows in arrival order: ">=" lets the later of equals take a
+        # "last" side, "<" keeps the earlier of equals on a "first" one.
+        for k, t, v in zip(keys, ts, vals):
+            kw = (k, (t - self.align_ms) // self.len_ms)
+            cell = self._table.get(kw)
+            if cell is None:
+                cell = self._table[kw] = [None, None, None, None]
+            cur = cell[2 * side]
+            if cur is None or (t < cur if self.first else t >= cur):
+                cell[2 * side] = t
+                cell[2 * side + 1] = v
+        mx_ts = batch.max_ts
+        if mx_ts is None and ts:
+            mx_ts = max(ts)
+        if mx_ts is not None and mx_ts > self.max_ts_host:
+            self.max_ts_host = mx_ts
+
+    def _win_lo(self) -> int:
+        return max(self.closed_horizon, -(1 << 39))
+
+    def _take(self, n: int, cols) -> Dict[str, Any]:
+        return {name: self.out[name][:n].clone() for name in cols}
+
+    def _check(self, n: int) -> None:
+        if n > self.out_cap:
+            msg = f"window join extract produced {n} rows > out_cap"
+            raise RuntimeError(msg)
+        _check_error_flag(int(self.error_flag.item()), "window join table")
+
+    def extract(
+        self,
+        horizon: Optional[int] = None,
+        clear: bool = True,
+        stamps: bool = False,
+    ) -> Optional[Dict[str, Any]]:
+        """The cells of windows in [closed_horizon, horizon) (up to
+        +inf if None) without reclaiming anything; the device table is
+        not mutated (`clear` drops the rows from the CPU twin only, as
+        `StatsAggState.extract` does).  With `stamps` the winning
+        timestamps come along as `t0` and `t1`."""
+        import torch
+
+        if horizon is None:
+            horizon = 1 << 40
+        win_lo = self._win_lo()
+        cols = _WJOIN_COLS + (("t0", "t1") if stamps else ())
+        if self.cpu:
+            hit = [
+                (k, w, c)
+                for (k, w), c in self._table.items()
+                if win_lo <= w < horizon
+            ]
+            if clear:
+                for k, w, _c in hit:
+                    del self._table[(k, w)]
+            rows = _wjoin_rows(hit)
+            if rows is not None and stamps:
+                for name, j in (("t0", 0), ("t1", 2)):
+                    rows[name] = torch.tensor(
+                        [0 if c[j] is None else c[j] for *_x, c in hit],
+                        dtype=torch.int64,
+                    )
+            return rows
+        self.out_n.zero_()
+        self.k.wjoin_extract(
+            self.tkeys, self.tts0, self.tts1, self.tv0, self.tv1,
+            win_lo, horizon, self.ts_none,
+            *(self.out[c] for c in ("keys", "wins", "v0", "v1", "t0", "t1")),
+            self.out["mask"], self.out_n,
+        )
+        n = int(self.out_n.item())
+        self._check(n)
+        if n == 0:
+            return None
+        return self._take(n, cols)
+
+    def close_due(
+        self, wait_ms: Optional[int] = None
+    ) -> Optional[Dict[str, Any]]:
+        """Emit every window fully below the watermark (`max_ts_host`
+        minus `wait_ms`, the constructor's by default) and reclaim its
+        space; None when nothing was due.  See :meth:`close_below`."""
+        return self.close_below(self.horizon_for(self.max_ts_host, wait_ms))
+
+    def horizon_for(
+        self, watermark_ms: int, wait_ms: Optional[int] = None
+    ) -> int:
+        """The window horizon of a watermark: every window below it
+        ends at or before `watermark_ms` minus `wait_ms` (the
+        constructor's by default).  What :meth:`close_below` takes."""
+        if wait_ms is None:
+            wait_ms = self.wait_ms
+        return (watermark_ms - wait_ms - self.align_ms) // self.len_ms
+
+    def close_eof(self) -> Optional[Dict[str, Any]]:
+        """End of input, as the operator closes it: every cell at or
+        above the closed horizon, with the horizon left where it is."""
+        return self.extract(None, clear=True)
+
+    def close_all(self) -> Optional[Dict[str, Any]]:
+        """EOF: every cell at or above the closed horizon, read without
+        mutating the device table; nothing is emitted after it."""
+        out = self.extract(None, clear=True)
+        self.closed_horizon = 1 << 40
+        return out
+
+    def close_below(self, horizon: int) -> Optional[Dict[str, Any]]:
+        """Close with reclamation: return the cells of windows in
+        [closed_horizon, horizon), each exactly once, keep the cells at
+        or above `horizon`, forget everything below it and advance
+        `closed_horizon` to `horizon`.
+
+        On device the live cells are rebuilt in a second table (see
+        k_wjoin_close_migrate), the tables are swapped and the retired
+        one is reset on the stream, so the table only ever holds the
+        open windows.  The second table is allocated by the first
+        close that has rows to emit.  A cell below `closed_horizon`
+        (an event behind the watermark; nothing tracks lateness) was
+        never going to be emitted; it is dropped here."""
+        if horizon <= self.closed_horizon:
+            return None
+        win_lo = self._win_lo()
+        if self.cpu:
+            hit = [
+                (k, w, c)
+                for (k, w), c in self._table.items()
+                if win_lo <= w < horizon
+            ]
+            for kw in [kw for kw in self._table if kw[1] < horizon]:
+                del self._table[kw]
+            self.closed_horizon = horizon
+            return _wjoin_rows(hit)
+        if self.tables_alt is None:
+            # Until something is due there is nothing to reclaim.  The
+            # stream's first close with rows scans twice.
+            if self.extract(horizon, clear=False) is None:
+                self.closed_horizon = horizon
+                return None
+            self.tables_alt = self._new_table()
+        live = (
+            self.tkeys, self.tts0, self.tts1, self.tv0, self.tv1,
+            self.telect,
+        )
+        self.out_n.zero_()
+        self.k.wjoin_close_migrate(
+            *live[:5],
+            *self.tables_alt[:5],
+            win_lo,
+            min(horizon, 1 << 40),
+            self.ts_none,
+            *(self.out[c] for c in _WJOIN_COLS),
+            self.out_n,
+            self.error_flag,
+        )
+        (
+            self.tkeys, self.tts0, self.tts1, self.tv0, self.tv1,
+            self.telect,
+        ) = self.tables_alt
+        self.tables_alt = live
+        # Reset the retired table asynchronously for the next close.
+        # Its election words are idle already: every insert leaves
+        # them so.
+        for t, fill in zip(live[:5], self._fills):
+            t.fill_(fill)
+        n = int(self.out_n.item())
+        self._check(n)
+        self.closed_horizon = horizon
+        if n == 0:
+            return None
+        return self._take(n, _WJOIN_COLS)
+
+    def snapshot_to_host(self) -> Dict[str, Any]:
+        """Spill the live cells with their winning timestamps, the
+        closed horizon, the window geometry and the insert mode."""
+        out: Dict[str, Any] = {
+            "max_ts": self.max_ts_host,
+            "closed_horizon": self.closed_horizon,
+            "align_ms": self.align_ms,
+            "len_ms": self.len_ms,
+            "insert_mode": self.insert_mode,
+            "n": 0,
+        }
+        snap = self.extract(None, clear=False, stamps=True)
+        if snap is not None:
+            for name, t in snap.items():
+                out[name] = t.cpu().numpy().copy()
+            out["n"] = len(out["keys"])
+        return out
+
+    def restore_from_host(self, snap: Dict[str, Any]) -> None:
+        """Re-insert each present side as the event (key, winning
+        timestamp, value) through the ordinary insert: the timestamp
+        lies in the cell's window and wins an empty side again."""
+        import torch
+
+        theirs = (
+            snap.get("align_ms"), snap.get("len_ms"), snap.get("insert_mode")
+        )
+        mine = (self.align_ms, self.len_ms, self.insert_mode)
+        if theirs != mine:
+            msg = (
+                "snapshot of a window join with (align_ms, len_ms, "
+                f"insert_mode) = {theirs} cannot restore one with {mine}"
+            )
+            raise ValueError(msg)
+        if snap["n"]:
+            for side in (0, 1):
+                m = (snap["mask"] & (1 << side)) != 0
+                if not m.any():
+                    continue
+                self.insert(
+                    side,
+                    RecordBatch(
+                        torch.as_tensor(snap["keys"][m]).to(self.device),
+                        torch.as_tensor(snap[f"t{side}"][m]).to(self.device),
+                        torch.as_tensor(snap[f"v{side}"][m]).to(self.device),
+                        max_ts=snap["max_ts"],
+                    ),
+                )
+        self.max_ts_host = snap["max_ts"]
+        self.closed_horizon = snap["closed_horizon"]
 
 
 class SessionAggState:
