@@ -3378,6 +3378,8 @@ __global__ void k_join_extract(
 //           (-1: table full) so that the later passes do not probe.
 //           Under "first" an event that strictly lowers the stamp
 //           opens the cell's election word (WJ_IDLE -> WJ_OPEN).
+//           The LATE form first diverts events below the late cutoff
+//           to the late buffer (see late_append) with ev_slot -1.
 //   elect   every event whose ts equals the now final stamp bids its
 //           row index: atomicMax ("last") / atomicMin ("first") on the
 //           election word.  Under "first" only opened cells take bids.
@@ -3409,7 +3411,16 @@ __global__ void k_join_extract(
 // (stamps and ev_slot, then election words), and launches on one
 // stream run in order with their writes visible to the next.  Every
 // other writer of the table (close, resets, restore) is enqueued on
-// that stream too.
+// that stream too.  (4) Late rows (the `LATE` stamp pass).  An event
+// with t < late_cutoff stores ev_slot[i] = -1 and nothing else of the
+// table: it does not probe, lowers no stamp and opens no election
+// word.  ev_slot is a scratch that keeps the slots of earlier batches,
+// so that store is what takes the row out: elect and commit skip a
+// negative slot, hence a late row is in no pass's bidder set and (1)
+// and (2) hold over the accepted rows alone.  The late cursor is only
+// ever advanced by wave leaders, one atomicAdd of the wave's late
+// count each, and every late lane stores to its own rank above the
+// returned base, so rows neither collide nor leave holes.
 #define WJ_IDLE 0x7FFFFFFF  // "first": no election open
 #define WJ_OPEN 0x7FFFFFFE  // "first": stamp lowered, bids welcome
 
@@ -3418,10 +3429,11 @@ __device__ __forceinline__ constexpr long long wj_ts_none() {
   return FIRST ? INT64_MAX : INT64_MIN;
 }
 
-template <bool FIRST, typename TS = int64_t>
+template <bool FIRST, typename TS = int64_t, bool LATE = false>
 __global__ void k_wjoin_stamp(
     const int32_t* __restrict__ keys,
     const TS* __restrict__ ts,
+    const int64_t* __restrict__ vals,  // LATE only (the late row's value)
     int64_t n,
     uint64_t* __restrict__ tkeys,
     long long* __restrict__ tts,  // this side's stamps
@@ -3432,12 +3444,31 @@ __global__ void k_wjoin_stamp(
     int64_t ts_base,
     int32_t* __restrict__ ev_slot,
     unsigned long long* __restrict__ max_ts,
-    int* __restrict__ error_flag) {
+    int* __restrict__ error_flag,
+    int64_t late_cutoff,  // LATE only (see late_append)
+    int32_t* __restrict__ late_keys,
+    int64_t* __restrict__ late_ts,
+    int64_t* __restrict__ late_vals,
+    int* __restrict__ late_n,
+    int64_t late_cap) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t stride = gridDim.x * (int64_t)blockDim.x;
   int64_t local_max = 0;
   for (; i < n; i += stride) {
     int64_t t = (int64_t)ts[i] + ts_base;
+    if constexpr (LATE) {
+      // Every lane still in the loop votes; lanes past n have left it.
+      bool is_late = t < late_cutoff;
+      late_append<true>(
+          is_late, is_late ? keys[i] : 0, t, is_late ? vals[i] : 0,
+          late_keys, late_ts, late_vals, late_n, late_cap, error_flag);
+      if (is_late) {
+        // The scratch keeps earlier batches' slots: without this store
+        // the row would bid and commit into another cell.
+        ev_slot[i] = -1;
+        continue;
+      }
+    }
     if (t > local_max) local_max = t;
     int64_t win = floor_div(t - align_ms, len_ms);
     uint64_t packed =
@@ -3522,9 +3553,11 @@ __device__ __forceinline__ int wj_mask(
 //   w >= win_hi           migrate into the fresh table, both stamps
 //                         and both values;
 //   w < win_lo            drop.  Such a cell was made by an event
-//                         behind the closed horizon (there is no late
-//                         tracking); its window has been emitted and
-//                         no extract reads it.
+//                         behind the closed horizon; its window has
+//                         been emitted and no extract reads it.  Only
+//                         inserts without late tracking make one: the
+//                         LATE stamp pass accepts t >= wm - wait only,
+//                         whose window is at or above the horizon.
 // The caller swaps the tables afterwards and resets the retired one
 // (keys EMPTY, stamps `ts_none`, values 0, election words idle).
 // Election words are idle between inserts, so they are not migrated:
@@ -7198,7 +7231,7 @@ void join_extract(
 // commit launches of k_wjoin_stamp on the current stream.  `tts` and
 // `tval` are the side's arrays, `ev_slot` a scratch of at least n
 // int32.  `ts` is absolute int64 or int32 deltas against `ts_base`.
-void wjoin_insert(
+static void wjoin_insert_impl(
     torch::Tensor keys,
     torch::Tensor ts,
     torch::Tensor vals,
@@ -7212,7 +7245,8 @@ void wjoin_insert(
     int64_t align_ms,
     int64_t len_ms,
     int64_t ts_base,
-    bool first) {
+    bool first,
+    const LateSink* late) {
   check_dev(keys, torch::kInt32, "keys");
   check_dev(vals, torch::kInt64, "vals");
   check_dev(tkeys, torch::kInt64, "tkeys");
@@ -7247,15 +7281,22 @@ void wjoin_insert(
   auto run = [&](auto first_c, auto* tsp) {
     constexpr bool F = decltype(first_c)::value;
     using TSV = std::remove_cv_t<std::remove_pointer_t<decltype(tsp)>>;
-    hipLaunchKernelGGL(
-        (k_wjoin_stamp<F, TSV>), grid, block, 0, stream,
-        keys.data_ptr<int32_t>(), tsp, n,
-        (uint64_t*)tkeys.data_ptr<int64_t>(),
-        (long long*)tts.data_ptr<int64_t>(), telect.data_ptr<int32_t>(),
-        (uint64_t)(nslots - 1), align_ms, len_ms, ts_base,
-        ev_slot.data_ptr<int32_t>(),
-        (unsigned long long*)max_ts.data_ptr<int64_t>(),
-        error_flag.data_ptr<int32_t>());
+    auto stamp = [&](auto kern, auto... extra) {
+      hipLaunchKernelGGL(
+          kern, grid, block, 0, stream, keys.data_ptr<int32_t>(), tsp,
+          (const int64_t*)vals.data_ptr<int64_t>(), n,
+          (uint64_t*)tkeys.data_ptr<int64_t>(),
+          (long long*)tts.data_ptr<int64_t>(), telect.data_ptr<int32_t>(),
+          (uint64_t)(nslots - 1), align_ms, len_ms, ts_base,
+          ev_slot.data_ptr<int32_t>(),
+          (unsigned long long*)max_ts.data_ptr<int64_t>(),
+          error_flag.data_ptr<int32_t>(), extra...);
+    };
+    if (late != nullptr)
+      stamp(k_wjoin_stamp<F, TSV, true>, late->cutoff, late->keys, late->ts,
+            late->vals, late->n, late->cap);
+    else
+      stamp(k_wjoin_stamp<F, TSV, false>, NO_LATE_ARGS);
     hipLaunchKernelGGL(
         (k_wjoin_elect<F, TSV>), grid, block, 0, stream, tsp, n, ts_base,
         (const long long*)tts.data_ptr<int64_t>(),
@@ -7277,6 +7318,55 @@ void wjoin_insert(
     by_ts(std::true_type{});
   else
     by_ts(std::false_type{});
+}
+
+void wjoin_insert(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    torch::Tensor vals,
+    torch::Tensor tkeys,
+    torch::Tensor tts,
+    torch::Tensor tval,
+    torch::Tensor telect,
+    torch::Tensor ev_slot,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    bool first) {
+  wjoin_insert_impl(keys, ts, vals, tkeys, tts, tval, telect, ev_slot, max_ts,
+                    error_flag, align_ms, len_ms, ts_base, first, nullptr);
+}
+
+// Late-tracking form of wjoin_insert (see window_agg_insert_late): an
+// event with absolute t < late_cutoff goes to the late buffer with its
+// value and takes no part in the stamp, elect or commit pass.
+void wjoin_insert_late(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    torch::Tensor vals,
+    torch::Tensor tkeys,
+    torch::Tensor tts,
+    torch::Tensor tval,
+    torch::Tensor telect,
+    torch::Tensor ev_slot,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    bool first,
+    int64_t late_cutoff,
+    torch::Tensor late_keys,
+    torch::Tensor late_ts,
+    torch::Tensor late_vals,
+    torch::Tensor late_n) {
+  c10::optional<torch::Tensor> lv(late_vals);
+  LateSink sink =
+      make_late_sink(late_cutoff, late_keys, late_ts, lv, late_n, true);
+  wjoin_insert_impl(keys, ts, vals, tkeys, tts, tval, telect, ev_slot, max_ts,
+                    error_flag, align_ms, len_ms, ts_base, first, &sink);
 }
 
 static void check_wjoin_table(
@@ -8323,6 +8413,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Extract live join state (recovery snapshot)");
   m.def("wjoin_insert", &wjoin_insert,
         "Windowed join: insert one side's batch (stamp, elect, commit)");
+  m.def("wjoin_insert_late", &wjoin_insert_late,
+        "Windowed join insert that diverts events below the late cutoff "
+        "to a late buffer");
   m.def("wjoin_close_migrate", &wjoin_close_migrate,
         "Windowed join close: emit [win_lo, win_hi), migrate the cells "
         "at or above win_hi");

@@ -1239,7 +1239,10 @@ def window_join(
     side, minus `wait`): this operator does not track late events, and
     nothing checks the ordering — an event behind the watermark makes
     a cell in a window that has already been emitted, and the next
-    close drops it.  No event may lie before `align_to` (window -1 of
+    close drops it.  For disordered input use `win.join_window` over
+    the two RecordBatch streams: it lowers onto the same kernels with
+    late tracking and reports late events on `WindowOut.late`.  No
+    event may lie before `align_to` (window -1 of
     key -1 would pack to the table's empty-slot sentinel), timestamps
     lie strictly inside the int64 range and window ids within int32.
 

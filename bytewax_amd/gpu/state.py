@@ -1252,8 +1252,20 @@ class WindowJoinState:
     `wins`, `v0`, `v1` and `mask` (bit ``s`` set: side ``s`` present; a
     missing side's value column reads 0), and reclaims its slot.
     Values are arbitrary int64; timestamps lie strictly inside the
-    int64 range.  There is no late tracking: see `window_join` for the
-    ordering contract.
+    int64 range.
+
+    Without ``track_late`` (the default) nothing checks the ordering:
+    see `window_join` for the contract.  With ``track_late=True``
+    disordered batches are accepted and late events reported by the
+    batch-granular rule of `WindowAggState`: an event of side ``s``
+    with absolute ``ts < max_ts_host - wait_ms``, taken as it stands
+    before its batch, joins no cell, whether its window is still open
+    or not, and comes out of ``take_late(s)`` exactly once.  One late
+    buffer per side says where a row came from (`late_cap` bounds each;
+    0 sizes it from the batches).  An accepted event then has
+    ``ts >= watermark - wait_ms``, so its window is at or above
+    ``horizon_for(watermark)``: no cell is ever made behind the closed
+    horizon and the drop arm of the close is unreachable.
     """
 
     def __init__(
@@ -1265,6 +1277,8 @@ class WindowJoinState:
         slots_pow: int = 20,
         out_cap: int = 1 << 20,
         wait_ms: int = 0,
+        track_late: bool = False,
+        late_cap: int = 0,
     ):
         import torch
 
@@ -1283,6 +1297,17 @@ class WindowJoinState:
         self.insert_mode = insert_mode
         self.first = insert_mode == "first"
         self.wait_ms = wait_ms
+        self.track_late = track_late
+        #: One tracker per side: a late row has to say which side it
+        #: came from, and one insert call handles one side.
+        self._late = (
+            tuple(
+                _LateTracker(device, wait_ms, True, late_cap)
+                for _side in (0, 1)
+            )
+            if track_late
+            else None
+        )
         self.max_ts_host = 0
         self.closed_horizon = -(1 << 62)
         #: The second table (keys, ts0, ts1, v0, v1, elect) that a
@@ -1335,7 +1360,12 @@ class WindowJoinState:
         )
 
     def insert(self, side: int, batch: RecordBatch) -> None:
-        """Insert one side's batch (`side` 0 = left, 1 = right)."""
+        """Insert one side's batch (`side` 0 = left, 1 = right).  With
+        `track_late` the events below ``max_ts_host - wait_ms``, as it
+        stands before this batch, go to the side's late rows."""
+        self._insert(side, batch, self.track_late)
+
+    def _insert(self, side: int, batch: RecordBatch, classify: bool) -> None:
         import torch
 
         if side not in (0, 1):
@@ -1346,14 +1376,23 @@ class WindowJoinState:
             raise ValueError(msg)
         n = len(batch)
         if self.cpu:
-            self._insert_cpu(side, batch)
+            self._insert_cpu(side, batch, classify)
             return
         if n:
             if self.ev_slot.numel() < n:
                 self.ev_slot = torch.empty(
                     n * 5 // 4, dtype=torch.int32, device=self.device
                 )
-            self.k.wjoin_insert(
+            late_args = ()
+            if classify:
+                lt = self._late[side]
+                lt.reserve(n, self.error_flag)
+                late_args = (
+                    self.max_ts_host - self.wait_ms,
+                    lt.keys, lt.ts, lt.vals, lt.n,
+                )
+            fn = self.k.wjoin_insert_late if classify else self.k.wjoin_insert
+            fn(
                 batch.keys,
                 batch.ts,
                 batch.vals,
@@ -1368,20 +1407,50 @@ class WindowJoinState:
                 self.len_ms,
                 batch.ts_base,
                 self.first,
+                *late_args,
             )
+            if classify:
+                self._late[side].inserted()
         if batch.max_ts is not None:
             if batch.max_ts > self.max_ts_host:
                 self.max_ts_host = batch.max_ts
         elif n:
-            # No host-side hint: the watermark has to come back from
-            # the device.
+            # No host-side hint: the watermark (and with `track_late`
+            # the next cutoff) has to come back from the device.
             dev_max = int(self.max_ts_dev.item())
             if dev_max > self.max_ts_host:
                 self.max_ts_host = dev_max
 
-    def _insert_cpu(self, side: int, batch: RecordBatch) -> None:
+    def take_late(self, side: int) -> Optional[RecordBatch]:
+        """Drain the late events of `side` accumulated since the last
+        call (`track_late` only): `keys`, absolute int64 `ts`
+        (``ts_base`` 0) and `vals`, one row per late event, in no
+        defined order.  Synchronises with the device."""
+        if side not in (0, 1):
+            msg = f"window join side must be 0 or 1, not {side!r}"
+            raise ValueError(msg)
+        if self._late is None:
+            return None
+        return self._late[side].take(None if self.cpu else self.error_flag)
+
+    def late_drained(self) -> bool:
+        """True when :meth:`insert` had to drain late rows of either
+        side into the host-side carry (see
+        `WindowAggState.late_drained`)."""
+        return self._late is not None and any(
+            bool(lt.carry) for lt in self._late
+        )
+
+    def _insert_cpu(
+        self, side: int, batch: RecordBatch, classify: bool = False
+    ) -> None:
         import torch
 
+        if classify:
+            # The rule of the LATE stamp pass (see WindowAggState).
+            batch = _split_late_cpu(
+                batch, self.max_ts_host - self.wait_ms, self._late[side]
+            )
         keys = batch.keys.tolist()
         ts = (batch.ts.to(torch.int64) + batch.ts_base).tolist()
         vals = batch.vals.tolist()
@@ -1502,8 +1571,9 @@ class WindowJoinState:
         one is reset on the stream, so the table only ever holds the
         open windows.  The second table is allocated by the first
         close that has rows to emit.  A cell below `closed_horizon`
-        (an event behind the watermark; nothing tracks lateness) was
-        never going to be emitted; it is dropped here."""
+        (an event behind the watermark) was never going to be emitted;
+        it is dropped here.  Only a state without `track_late` can hold
+        one: with it such an event went to the late rows instead."""
         if horizon <= self.closed_horizon:
             return None
         win_lo = self._win_lo()
@@ -1558,13 +1628,17 @@ class WindowJoinState:
 
     def snapshot_to_host(self) -> Dict[str, Any]:
         """Spill the live cells with their winning timestamps, the
-        closed horizon, the window geometry and the insert mode."""
+        closed horizon, the window geometry, the insert mode and
+        `track_late`.  Late rows not yet taken are not part of it: the
+        caller drains them through :meth:`take_late` and persists them
+        itself (as `_ColumnarJoinLogic` does)."""
         out: Dict[str, Any] = {
             "max_ts": self.max_ts_host,
             "closed_horizon": self.closed_horizon,
             "align_ms": self.align_ms,
             "len_ms": self.len_ms,
             "insert_mode": self.insert_mode,
+            "track_late": self.track_late,
             "n": 0,
         }
         snap = self.extract(None, clear=False, stamps=True)
@@ -1576,8 +1650,14 @@ class WindowJoinState:
 
     def restore_from_host(self, snap: Dict[str, Any]) -> None:
         """Re-insert each present side as the event (key, winning
-        timestamp, value) through the ordinary insert: the timestamp
-        lies in the cell's window and wins an empty side again."""
+        timestamp, value) through the insert without late tracking:
+        the timestamp lies in the cell's window and wins an empty side
+        again.  Restore never classifies: once side 0 is in with the
+        snapshot's `max_ts`, a side-1 stamp of a still open window may
+        lie below ``max_ts - wait_ms``, and it was accepted when it
+        arrived.  A snapshot taken with `track_late` restores only into
+        a state that has it too (its stream may be disordered); one
+        taken without restores into either kind."""
         import torch
 
         theirs = (
@@ -1590,12 +1670,18 @@ class WindowJoinState:
                 f"insert_mode) = {theirs} cannot restore one with {mine}"
             )
             raise ValueError(msg)
+        if snap.get("track_late", False) and not self.track_late:
+            msg = (
+                "snapshot of a window join with track_late=True cannot "
+                "restore one without late tracking"
+            )
+            raise ValueError(msg)
         if snap["n"]:
             for side in (0, 1):
                 m = (snap["mask"] & (1 << side)) != 0
                 if not m.any():
                     continue
-                self.insert(
+                self._insert(
                     side,
                     RecordBatch(
                         torch.as_tensor(snap["keys"][m]).to(self.device),
@@ -1603,6 +1689,7 @@ class WindowJoinState:
                         torch.as_tensor(snap[f"v{side}"][m]).to(self.device),
                         max_ts=snap["max_ts"],
                     ),
+                    False,
                 )
         self.max_ts_host = snap["max_ts"]
         self.closed_horizon = snap["closed_horizon"]

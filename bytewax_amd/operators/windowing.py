@@ -910,6 +910,28 @@ def device_mean(value_getter: Callable = _identity) -> DeviceFoldable:
     )
 
 
+#: `device_mode` of a lowerable `join_window` -> the state's insert mode.
+_JOIN_DEVICE_MODES = {"join_first": "first", "join_last": "last"}
+
+
+def _join_device_mode(
+    side_count: int, clock, insert_mode: str, emit_mode: str, ordered: bool
+) -> Optional[str]:
+    """The `device_mode` that `join_window` hands to `window`: set for
+    exactly two sides, an `EventClock`, "final" emit, "first" or
+    "last" insert and ``ordered=True`` (unordered, arrival order
+    decides the winner, which the device's timestamp rule is not)."""
+    if (
+        side_count == 2
+        and isinstance(clock, EventClock)
+        and emit_mode == "final"
+        and insert_mode in ("first", "last")
+        and ordered
+    ):
+        return f"join_{insert_mode}"
+    return None
+
+
 @dataclass
 class _ColumnarSpec:
     """Device-lowering parameters resolved from clock + windower."""
@@ -926,9 +948,21 @@ class _ColumnarSpec:
         EventClock (RecordBatch.ts IS the event timestamp), and the
         windower is tumbling/sliding, or a session windower with a
         count/sum fold (`_ColumnarSessionSpec`; session min/max/mean
-        stay on the host)."""
+        stay on the host).  The `join_window` modes ("join_first" /
+        "join_last") lower for a `TumblingWindower` only
+        (`_ColumnarJoinSpec`)."""
         if mode is None or not isinstance(clock, EventClock):
             return None
+        if mode in _JOIN_DEVICE_MODES:
+            if not isinstance(windower, TumblingWindower):
+                # Sliding and session joins stay on the host.
+                return None
+            return _ColumnarJoinSpec(
+                _JOIN_DEVICE_MODES[mode],
+                int((windower.align_to - _EPOCH_UTC).total_seconds() * 1000),
+                int(windower.length.total_seconds() * 1000),
+                int(clock.wait_for_system_duration.total_seconds() * 1000),
+            )
         if isinstance(windower, SessionWindower):
             if mode not in ("count", "sum"):
                 return None
@@ -1265,11 +1299,187 @@ class _ColumnarSessionLogic(StatefulBatchLogic):
         return {"__columnar__": self.state.snapshot_to_host()}
 
 
+@dataclass
+class _ColumnarJoinSpec:
+    """Device-lowering parameters of `join_window`: two sides,
+    `EventClock`, `TumblingWindower`, "first"/"last" insert, "final"
+    emit, ordered."""
+
+    insert_mode: str
+    align_ms: int
+    len_ms: int
+    wait_ms: int
+
+    def build(self, resume) -> "_ColumnarJoinLogic":
+        return _ColumnarJoinLogic(self, resume)
+
+
+class _ColumnarJoinLogic(StatefulBatchLogic):
+    """The columnar engine behind a lowered `join_window`:
+    `WindowJoinState(track_late=True)`.
+
+    Values are `(side, RecordBatch)`, as `_join_label_merge` labels
+    them.  Emissions under `COLUMNAR_WINDOW_ID`:
+
+    - ``"E"``: the five-column dict of `gpu.operators.window_join`
+      (`keys`, `wins`, `v0`, `v1`, `mask`), one row per (key, window)
+      cell, once per close that has rows and at EOF.  `wins` are the
+      host's window ids: ``(ts - align_to) // length``.
+    - ``"L"``: `(side, RecordBatch(keys, absolute ts, vals))`,
+      mirroring the host, whose late values are `(side, value)`.  One
+      row is one late event.
+    - no ``"M"``: like the other tumbling lowerings this one emits no
+      window metadata; a window's bounds follow from its id.
+
+    Lateness is batch-granular, as on `_ColumnarWindowLogic`: an event
+    below the maximum of all EARLIER batches (of either side) minus
+    the clock's wait is late, whether its window is still open or not.
+    Late rows are read back only where the host synchronises anyway: a
+    close that ran, EOF, a snapshot, or a drain forced by the state's
+    late buffer.  Rows drained by `snapshot()` are persisted per side
+    under ``"__late__"`` and go out on the next activation or after a
+    resume.
+    """
+
+    def __init__(self, spec: _ColumnarJoinSpec, resume):
+        self.spec = spec
+        self.state = None  # built on first batch (device known then)
+        self._resume = resume
+        #: Per side, late RecordBatches drained but not yet emitted.
+        self._late_carry: Tuple[List, List] = ([], [])
+        if isinstance(resume, dict) and resume.get("__late__") is not None:
+            from ..gpu import RecordBatch
+            import torch
+
+            for side, saved in enumerate(resume["__late__"]):
+                if saved is None:
+                    continue
+                self._late_carry[side].append(
+                    RecordBatch(
+                        torch.as_tensor(saved["keys"]),
+                        torch.as_tensor(saved["ts"]),
+                        torch.as_tensor(saved["vals"]),
+                    )
+                )
+
+    def _ensure(self, batch) -> None:
+        if self.state is not None:
+            return
+        from ..gpu.state import WindowJoinState
+
+        dev = batch.keys.device
+        on_gpu = dev.type != "cpu"
+        self.state = WindowJoinState(
+            dev,
+            self.spec.align_ms,
+            self.spec.len_ms,
+            self.spec.insert_mode,
+            slots_pow=22 if on_gpu else 16,
+            out_cap=1 << (22 if on_gpu else 16),
+            wait_ms=self.spec.wait_ms,
+            track_late=True,
+        )
+        if self._resume is not None:
+            self.state.restore_from_host(self._resume)
+            self._resume = None
+
+    def _drain_late(self) -> None:
+        """Move the state's late rows into the carry (synchronises)."""
+        for side in (0, 1):
+            late = self.state.take_late(side)
+            if late is not None:
+                self._late_carry[side].append(late)
+
+    def _late_events(self) -> List:
+        events = []
+        for side in (0, 1):
+            events.extend(
+                (COLUMNAR_WINDOW_ID, "L", (side, late))
+                for late in self._late_carry[side]
+            )
+            self._late_carry[side].clear()
+        return events
+
+    def on_batch(self, values) -> Tuple[Iterable, bool]:
+        events: List = []
+        for side, batch in values:
+            self._ensure(batch)
+            self.state.insert(side, batch)
+        if self.state is None:
+            return (self._late_events(), False)
+        was_closed = self.state.closed_horizon
+        closed = self.state.close_due()
+        if closed is not None:
+            events.append((COLUMNAR_WINDOW_ID, "E", closed))
+        # Late rows come back where the host synchronised anyway: a
+        # close that ran, or a drain the state's buffer bound forced.
+        if (
+            self.state.closed_horizon != was_closed
+            or self.state.late_drained()
+        ):
+            self._drain_late()
+        events.extend(self._late_events())
+        return (events, False)
+
+    def on_notify(self) -> Tuple[Iterable, bool]:
+        return (self._late_events(), False)
+
+    def on_eof(self) -> Tuple[Iterable, bool]:
+        if self.state is None:
+            return (self._late_events(), True)
+        final = self.state.close_all()
+        self._drain_late()
+        events = self._late_events()
+        if final is not None:
+            events.insert(0, (COLUMNAR_WINDOW_ID, "E", final))
+        return (events, True)
+
+    def notify_at(self) -> Optional[datetime]:
+        return None
+
+    def _late_snapshot(self):
+        """Carried late rows per side as host arrays (None for a side
+        without any)."""
+        import torch
+
+        out = []
+        for carry in self._late_carry:
+            if not carry:
+                out.append(None)
+                continue
+            out.append(
+                {
+                    name: torch.cat([getattr(b, name).cpu() for b in carry])
+                    .numpy()
+                    .copy()
+                    for name in ("keys", "ts", "vals")
+                }
+            )
+        return out
+
+    def snapshot(self):
+        # Cannot emit: rows drained here are carried and persisted, and
+        # go out on the next activation (or after a resume).
+        if self.state is None:
+            snap = dict(self._resume) if self._resume is not None else None
+        else:
+            self._drain_late()
+            snap = self.state.snapshot_to_host()
+        if snap is not None:
+            snap["__late__"] = self._late_snapshot()
+        return {"__columnar__": snap}
+
+
+def _is_record_batch(v) -> bool:
+    return hasattr(v, "keys") and hasattr(v, "ts") and hasattr(v, "ts_base")
+
+
 class _AutoWindowLogic(StatefulBatchLogic):
     """Engine dispatch for `window`: host `_WindowLogic` for
     Python-object values, the fused HIP kernels for RecordBatch values
-    — decided on the first batch (streams are dynamically typed), and
-    persisted through snapshots."""
+    (`(side, RecordBatch)` pairs under a join spec) — decided on the
+    first batch (streams are dynamically typed), and persisted through
+    snapshots."""
 
     def __init__(self, host_builder, spec: Optional[_ColumnarSpec], resume):
         self._host_builder = host_builder
@@ -1285,12 +1495,14 @@ class _AutoWindowLogic(StatefulBatchLogic):
         if self._impl is not None:
             return
         v = values[0] if values else None
-        if (
-            self._spec is not None
-            and hasattr(v, "keys")
-            and hasattr(v, "ts")
-            and hasattr(v, "ts_base")
-        ):
+        if isinstance(self._spec, _ColumnarJoinSpec):
+            # The merged join stream carries (side, value).
+            columnar = (
+                isinstance(v, tuple) and len(v) == 2 and _is_record_batch(v[1])
+            )
+        else:
+            columnar = self._spec is not None and _is_record_batch(v)
+        if columnar:
             self._impl = self._spec.build(None)
         else:
             self._impl = self._host_builder(None)
@@ -1862,6 +2074,20 @@ def join_window(
     :returns: Window result streams; downstream contains tuples with
         the value from each side in argument order.
 
+    Two sides of `gpu.RecordBatch` values lower onto the device join
+    (`WindowJoinState` with late tracking) when the clock is an
+    `EventClock`, the windower a `TumblingWindower`, `insert_mode` is
+    "first" or "last", `emit_mode` is "final" and `ordered` is true;
+    every other configuration, and every stream of Python objects,
+    runs on the host as before.  The lowered step emits under
+    `COLUMNAR_WINDOW_ID`: `down` carries dicts of columns `keys`,
+    `wins` (the window ids), `v0`, `v1` and `mask` (bit ``s`` set:
+    side ``s`` present), one row per (key, window); `late` carries
+    `(side, RecordBatch)` with one row per late event, late by the
+    batch-granular watermark (the maximum over all earlier batches of
+    either side, minus the clock's wait); `meta` stays empty, a
+    tumbling window's bounds follow from its id.
+
     Example:
 
     >>> align = datetime(2024, 1, 1, tzinfo=timezone.utc)
@@ -1925,5 +2151,13 @@ def join_window(
         return _JoinWindowLogic(insert_mode, emit_mode, state)
 
     return window(
-        "window", merged, clock, windower, shim_builder, ordered=ordered
+        "window",
+        merged,
+        clock,
+        windower,
+        shim_builder,
+        ordered=ordered,
+        device_mode=_join_device_mode(
+            side_count, clock, insert_mode, emit_mode, ordered
+        ),
     )
