@@ -3749,6 +3749,241 @@ __global__ void k_wjoin_extract(
   }
 }
 
+// Sliding windowed join close: two passes over the pane table.  The
+// table holds one cell per (key, pane), a pane being a tumbling window
+// of gcd(length, offset); the geometry is k_stats_pane_close's: window
+// `w` is the `L` panes [w * o, w * o + L), pane `p` lies in the windows
+// floor((p - L) / o) + 1 .. floor(p / o), clipped to [win_lo, win_hi)
+// and to >= 1 - L, and the fold table stores w + L in the high key half
+// so that (w = -1, key = -1) does not pack to EMPTY_SLOT.  A window
+// below 1 - L (an event before `align`, which the sliding join does not
+// support) is skipped.
+//
+// The fold table is five arrays (keys, ts0, ts1, v0, v1; no election
+// words), EMPTY / ts_none / ts_none / 0 / 0 when the stamp pass starts.
+// A side of a fold cell is a (stamp, value) pair, which no single
+// commuting atomic merges; hence
+//   stamp   (k_wjoin_pane_stamp) every occupied pane cell with a side
+//           claims (key, w + L) for each of its windows in range and
+//           does atomicMax ("last") / atomicMin ("first") of each
+//           present side's pane stamp on that side's fold stamp.  A
+//           cell with p >= pane_keep is also copied into the fresh
+//           pane table (both stamps, both values), exactly as
+//           k_wjoin_close_migrate migrates; the others are dropped.
+//   commit  (k_wjoin_pane_commit) the same walk over the old pane
+//           table, which the stamp pass has not written: per window in
+//           range and present side the fold cell is looked up again
+//           (find only, no claim), and the pane whose stamp equals the
+//           fold stamp stores its value plainly.
+// The rows are then read with k_wjoin_extract over the fold table; the
+// caller subtracts L from the window column and refills the table.
+//
+// The chunked shape is k_wjoin_close_migrate's: 16-byte key loads,
+// CM_CHUNK slots per block step, stamps and values read only for a
+// cell that is folded or migrated.  No row reservation, so no LDS and
+// no barrier.
+//
+// Exactness.  (1) Who may write a fold value: only the commit pass, and
+// there only a pane cell whose side stamp equals the fold cell's.
+// (2) That writer is unique and is the winner.  The panes of a window
+// are disjoint in time and a side's stamp is the timestamp of an event
+// of that pane, so the stamps of one (key, side) in different panes are
+// pairwise different.  After the stamp pass a fold stamp is the max
+// ("last") / min ("first") of the stamps of the window's panes that
+// hold the side, atomics being total per address and `ts_none` their
+// identity; exactly one pane equals it.  The side of window `w` under
+// "last" is the event with the greatest (ts, arrival) over the window:
+// it lies in the pane with the greatest stamp, and within that pane the
+// insert has already applied the arrival tie rule, equal timestamps
+// never spanning two panes.  "first" mirrors it.  (3) Launch order is
+// enough: the commit reads only fold keys and stamps, which the stamp
+// pass finished writing before the commit starts on the same stream,
+// and the old pane table, which neither pass writes; the extract is
+// the next launch after the commit, and the refills follow it.  Every
+// other writer of the three tables (insert, resets, restore) is
+// enqueued on that stream too.  Migration: as k_wjoin_close_migrate,
+// the target is fresh and each migrated cell unique.
+__device__ __forceinline__ bool wj_pane_windows(
+    uint64_t cell, int64_t win_lo, int64_t win_hi, int64_t L, int64_t o,
+    int64_t* p, int64_t* lo, int64_t* hi) {
+  *p = (int64_t)(int32_t)(uint32_t)(cell >> 32);
+  int64_t a = floor_div(*p - L, o) + 1;
+  int64_t b = floor_div(*p, o);
+  if (a < win_lo) a = win_lo;
+  if (a < 1 - L) a = 1 - L;
+  if (b > win_hi - 1) b = win_hi - 1;
+  *lo = a;
+  *hi = b;
+  return a <= b;
+}
+
+// Find-only probe (no claim): the slot of `packed` or ~0 if absent.
+__device__ __forceinline__ uint64_t lookup_slot(
+    const uint64_t* __restrict__ tkeys, uint64_t mask, uint64_t packed) {
+  uint64_t h = mix64(packed) & mask;
+  for (uint64_t probes = 0; probes <= mask; ++probes) {
+    uint64_t cur = tkeys[h];
+    if (cur == packed) return h;
+    if (cur == EMPTY_SLOT) return ~0ULL;
+    h = (h + 1) & mask;
+  }
+  return ~0ULL;
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(CM_BLK) void k_wjoin_pane_stamp(
+    const uint64_t* __restrict__ tkeys,
+    const long long* __restrict__ tts0,
+    const long long* __restrict__ tts1,
+    const long long* __restrict__ tv0,
+    const long long* __restrict__ tv1,
+    int64_t nslots,
+    int64_t win_lo,
+    int64_t win_hi,
+    int64_t pane_keep,
+    int64_t L,
+    int64_t o,
+    uint64_t* __restrict__ nkeys,
+    long long* __restrict__ nts0,
+    long long* __restrict__ nts1,
+    long long* __restrict__ nv0,
+    long long* __restrict__ nv1,
+    uint64_t mask,
+    uint64_t* __restrict__ fkeys,
+    long long* __restrict__ fts0,
+    long long* __restrict__ fts1,
+    uint64_t fmask,
+    int* __restrict__ error_flag) {
+  constexpr long long ts_none = wj_ts_none<FIRST>();
+  const bool vec = (((uintptr_t)tkeys) & 15) == 0;
+  const int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    // Slot of k[q]: s0 + (q / 2) * (CM_BLK * 2) + (q & 1).
+    const int64_t s0 = c * CM_CHUNK + threadIdx.x * 2;
+    uint64_t k[CM_PER];
+    for (int j = 0; j < CM_PER / 2; ++j) {
+      int64_t s = s0 + (int64_t)j * (CM_BLK * 2);
+      if (vec && s + 1 < nslots) {
+        ulonglong2 kk = *(const ulonglong2*)(tkeys + s);
+        k[2 * j] = kk.x;
+        k[2 * j + 1] = kk.y;
+      } else {
+        for (int q = 0; q < 2; ++q) {
+          k[2 * j + q] = s + q < nslots ? tkeys[s + q] : EMPTY_SLOT;
+        }
+      }
+    }
+    for (int q = 0; q < CM_PER; ++q) {
+      if (k[q] == EMPTY_SLOT) continue;
+      int64_t p, lo, hi;
+      const bool fold =
+          wj_pane_windows(k[q], win_lo, win_hi, L, o, &p, &lo, &hi);
+      const bool keep = p >= pane_keep;
+      if (!fold && !keep) continue;
+      int64_t s = s0 + (int64_t)(q >> 1) * (CM_BLK * 2) + (q & 1);
+      const long long a0 = tts0[s], a1 = tts1[s];
+      // A cell with no side (see k_wjoin_close_migrate) makes no row.
+      if (fold && wj_mask(a0, a1, ts_none) != 0) {
+        const uint64_t key = k[q] & 0xFFFFFFFFULL;
+        for (int64_t w = lo; w <= hi; ++w) {
+          uint64_t packed = ((uint64_t)(uint32_t)(int32_t)(w + L) << 32) | key;
+          uint64_t slot = find_slot(fkeys, fmask, packed);
+          if (slot == ~0ULL) {
+            atomicOr(error_flag, 1);
+            break;
+          }
+          if constexpr (FIRST) {
+            if (a0 != ts_none) atomicMin(&fts0[slot], a0);
+            if (a1 != ts_none) atomicMin(&fts1[slot], a1);
+          } else {
+            if (a0 != ts_none) atomicMax(&fts0[slot], a0);
+            if (a1 != ts_none) atomicMax(&fts1[slot], a1);
+          }
+        }
+      }
+      if (keep) {
+        long long b0 = tv0[s], b1 = tv1[s];
+        uint64_t slot = find_slot(nkeys, mask, k[q]);
+        if (slot == ~0ULL) {
+          atomicOr(error_flag, 1);
+        } else {
+          nts0[slot] = a0;
+          nts1[slot] = a1;
+          nv0[slot] = b0;
+          nv1[slot] = b1;
+        }
+      }
+    }
+  }
+}
+
+// The commit pass of the sliding join close (see k_wjoin_pane_stamp,
+// whose walk and window ranges this repeats).  Only finds, no claims:
+// the stamp pass claimed every fold cell looked up here, so a missing
+// one means that pass ran out of fold slots (it has raised the flag
+// already) and is reported the same way.
+__global__ __launch_bounds__(CM_BLK) void k_wjoin_pane_commit(
+    const uint64_t* __restrict__ tkeys,
+    const long long* __restrict__ tts0,
+    const long long* __restrict__ tts1,
+    const long long* __restrict__ tv0,
+    const long long* __restrict__ tv1,
+    int64_t nslots,
+    int64_t win_lo,
+    int64_t win_hi,
+    int64_t L,
+    int64_t o,
+    long long ts_none,
+    const uint64_t* __restrict__ fkeys,
+    const long long* __restrict__ fts0,
+    const long long* __restrict__ fts1,
+    long long* __restrict__ fv0,
+    long long* __restrict__ fv1,
+    uint64_t fmask,
+    int* __restrict__ error_flag) {
+  const bool vec = (((uintptr_t)tkeys) & 15) == 0;
+  const int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    // Slot of k[q]: s0 + (q / 2) * (CM_BLK * 2) + (q & 1).
+    const int64_t s0 = c * CM_CHUNK + threadIdx.x * 2;
+    uint64_t k[CM_PER];
+    for (int j = 0; j < CM_PER / 2; ++j) {
+      int64_t s = s0 + (int64_t)j * (CM_BLK * 2);
+      if (vec && s + 1 < nslots) {
+        ulonglong2 kk = *(const ulonglong2*)(tkeys + s);
+        k[2 * j] = kk.x;
+        k[2 * j + 1] = kk.y;
+      } else {
+        for (int q = 0; q < 2; ++q) {
+          k[2 * j + q] = s + q < nslots ? tkeys[s + q] : EMPTY_SLOT;
+        }
+      }
+    }
+    for (int q = 0; q < CM_PER; ++q) {
+      if (k[q] == EMPTY_SLOT) continue;
+      int64_t p, lo, hi;
+      if (!wj_pane_windows(k[q], win_lo, win_hi, L, o, &p, &lo, &hi)) continue;
+      int64_t s = s0 + (int64_t)(q >> 1) * (CM_BLK * 2) + (q & 1);
+      const long long a0 = tts0[s], a1 = tts1[s];
+      if (wj_mask(a0, a1, ts_none) == 0) continue;
+      const long long b0 = tv0[s], b1 = tv1[s];
+      const uint64_t key = k[q] & 0xFFFFFFFFULL;
+      for (int64_t w = lo; w <= hi; ++w) {
+        uint64_t packed = ((uint64_t)(uint32_t)(int32_t)(w + L) << 32) | key;
+        uint64_t slot = lookup_slot(fkeys, fmask, packed);
+        if (slot == ~0ULL) {
+          atomicOr(error_flag, 1);
+          break;
+        }
+        // `ts_none` is no event's timestamp, so an absent side never
+        // compares equal to a fold stamp some other pane has set.
+        if (a0 != ts_none && fts0[slot] == a0) fv0[slot] = b0;
+        if (a1 != ts_none && fts1[slot] == a1) fv1[slot] = b1;
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Session windows (gap-based).  Per-key state is one table cell:
 // (session_start, last_ts, accumulator).  Batches arrive SORTED by
@@ -7495,6 +7730,141 @@ void wjoin_extract(
       out_n.data_ptr<int32_t>(), cap);
 }
 
+// Checks shared by the two passes of the sliding join close; returns
+// the grid.  `max_blocks` (0: the usual cap) lets a caller force the
+// grid stride on a small table.
+static unsigned check_wjoin_pane_close(
+    const torch::Tensor& tkeys, const torch::Tensor& fkeys,
+    const torch::Tensor* const* fcols, int64_t panes_per_window,
+    int64_t panes_per_offset, const torch::Tensor& error_flag,
+    int64_t max_blocks) {
+  check_wjoin_table(fkeys, fcols, 4);
+  TORCH_CHECK(fkeys.data_ptr() != tkeys.data_ptr(),
+              "the pane table and the fold table must be distinct");
+  check_dev(error_flag, torch::kInt32, "error_flag");
+  TORCH_CHECK(error_flag.numel() >= 1, "error_flag must hold one element");
+  TORCH_CHECK(panes_per_offset >= 1 && panes_per_window >= panes_per_offset &&
+                  panes_per_window <= 64,
+              "need 1 <= panes per offset <= panes per window <= 64");
+  TORCH_CHECK(max_blocks >= 0, "max_blocks must not be negative");
+  int64_t cap = max_blocks > 0 && max_blocks < CM_MAX_GRID ? max_blocks
+                                                           : CM_MAX_GRID;
+  int64_t nchunks = (tkeys.numel() + CM_CHUNK - 1) / CM_CHUNK;
+  return (unsigned)(nchunks < cap ? nchunks : cap);
+}
+
+// Stamp pass of the sliding join close (see k_wjoin_pane_stamp): folds
+// the stamps of the panes of the windows in [win_lo, win_hi) into the
+// fold table `f*` and migrates the panes at or above `pane_keep` into
+// the fresh table `n*`.  wjoin_pane_commit has to follow on the stream.
+void wjoin_pane_stamp(
+    torch::Tensor tkeys,
+    torch::Tensor tts0,
+    torch::Tensor tts1,
+    torch::Tensor tv0,
+    torch::Tensor tv1,
+    torch::Tensor nkeys,
+    torch::Tensor nts0,
+    torch::Tensor nts1,
+    torch::Tensor nv0,
+    torch::Tensor nv1,
+    torch::Tensor fkeys,
+    torch::Tensor fts0,
+    torch::Tensor fts1,
+    torch::Tensor fv0,
+    torch::Tensor fv1,
+    int64_t win_lo,
+    int64_t win_hi,
+    int64_t pane_keep,
+    int64_t panes_per_window,
+    int64_t panes_per_offset,
+    bool first,
+    torch::Tensor error_flag,
+    int64_t max_blocks) {
+  const torch::Tensor* live[] = {&tts0, &tts1, &tv0, &tv1};
+  const torch::Tensor* fresh[] = {&nts0, &nts1, &nv0, &nv1};
+  const torch::Tensor* fold[] = {&fts0, &fts1, &fv0, &fv1};
+  check_wjoin_table(tkeys, live, 4);
+  check_wjoin_table(nkeys, fresh, 4);
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK(nkeys.numel() == nslots, "table size mismatch");
+  TORCH_CHECK(nkeys.data_ptr() != tkeys.data_ptr() &&
+                  fkeys.data_ptr() != nkeys.data_ptr(),
+              "the three tables must be distinct");
+  unsigned grid = check_wjoin_pane_close(
+      tkeys, fkeys, fold, panes_per_window, panes_per_offset, error_flag,
+      max_blocks);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(
+        kernel, dim3(grid), dim3(CM_BLK), 0, at::hip::getCurrentHIPStream(),
+        (const uint64_t*)tkeys.data_ptr<int64_t>(),
+        (const long long*)tts0.data_ptr<int64_t>(),
+        (const long long*)tts1.data_ptr<int64_t>(),
+        (const long long*)tv0.data_ptr<int64_t>(),
+        (const long long*)tv1.data_ptr<int64_t>(), nslots, win_lo, win_hi,
+        pane_keep, panes_per_window, panes_per_offset,
+        (uint64_t*)nkeys.data_ptr<int64_t>(),
+        (long long*)nts0.data_ptr<int64_t>(),
+        (long long*)nts1.data_ptr<int64_t>(),
+        (long long*)nv0.data_ptr<int64_t>(),
+        (long long*)nv1.data_ptr<int64_t>(), (uint64_t)(nslots - 1),
+        (uint64_t*)fkeys.data_ptr<int64_t>(),
+        (long long*)fts0.data_ptr<int64_t>(),
+        (long long*)fts1.data_ptr<int64_t>(),
+        (uint64_t)(fkeys.numel() - 1), error_flag.data_ptr<int32_t>());
+  };
+  if (first) {
+    launch(k_wjoin_pane_stamp<true>);
+  } else {
+    launch(k_wjoin_pane_stamp<false>);
+  }
+}
+
+// Commit pass of the sliding join close (see k_wjoin_pane_commit), over
+// the pane table wjoin_pane_stamp has just read, with the same window
+// range and geometry.
+void wjoin_pane_commit(
+    torch::Tensor tkeys,
+    torch::Tensor tts0,
+    torch::Tensor tts1,
+    torch::Tensor tv0,
+    torch::Tensor tv1,
+    torch::Tensor fkeys,
+    torch::Tensor fts0,
+    torch::Tensor fts1,
+    torch::Tensor fv0,
+    torch::Tensor fv1,
+    int64_t win_lo,
+    int64_t win_hi,
+    int64_t panes_per_window,
+    int64_t panes_per_offset,
+    bool first,
+    torch::Tensor error_flag,
+    int64_t max_blocks) {
+  const torch::Tensor* live[] = {&tts0, &tts1, &tv0, &tv1};
+  const torch::Tensor* fold[] = {&fts0, &fts1, &fv0, &fv1};
+  check_wjoin_table(tkeys, live, 4);
+  unsigned grid = check_wjoin_pane_close(
+      tkeys, fkeys, fold, panes_per_window, panes_per_offset, error_flag,
+      max_blocks);
+  hipLaunchKernelGGL(
+      k_wjoin_pane_commit, dim3(grid), dim3(CM_BLK), 0,
+      at::hip::getCurrentHIPStream(),
+      (const uint64_t*)tkeys.data_ptr<int64_t>(),
+      (const long long*)tts0.data_ptr<int64_t>(),
+      (const long long*)tts1.data_ptr<int64_t>(),
+      (const long long*)tv0.data_ptr<int64_t>(),
+      (const long long*)tv1.data_ptr<int64_t>(), tkeys.numel(), win_lo,
+      win_hi, panes_per_window, panes_per_offset,
+      (long long)(first ? INT64_MAX : INT64_MIN),
+      (const uint64_t*)fkeys.data_ptr<int64_t>(),
+      (const long long*)fts0.data_ptr<int64_t>(),
+      (const long long*)fts1.data_ptr<int64_t>(),
+      (long long*)fv0.data_ptr<int64_t>(),
+      (long long*)fv1.data_ptr<int64_t>(), (uint64_t)(fkeys.numel() - 1),
+      error_flag.data_ptr<int32_t>());
+}
+
 int64_t filter_compact(
     torch::Tensor keys,
     torch::Tensor ts,
@@ -8421,6 +8791,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "at or above win_hi");
   m.def("wjoin_extract", &wjoin_extract,
         "Windowed join: extract live cells with stamps (non-mutating)");
+  m.def("wjoin_pane_stamp", &wjoin_pane_stamp,
+        "Sliding windowed join close, stamp pass: fold the pane stamps of "
+        "due windows into a fold table, migrate live panes, drop dead ones");
+  m.def("wjoin_pane_commit", &wjoin_pane_commit,
+        "Sliding windowed join close, commit pass: the pane that holds a "
+        "fold stamp stores its value");
   m.def("filter_compact", &filter_compact,
         "Stream compaction of a RecordBatch by a boolean mask");
   m.def("bucket_hist", &bucket_hist, "Per-destination counts for exchange");

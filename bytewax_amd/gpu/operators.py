@@ -1206,11 +1206,13 @@ def window_join(
     out_cap: int = 1 << 20,
     device: str = "cuda",
     exchange: Optional[bool] = None,
+    offset: Optional[timedelta] = None,
+    fold_slots_pow: Optional[int] = None,
 ) -> Stream[Dict[str, Any]]:
-    """Two-sided join over tumbling event-time windows of columnar
-    batches on GPU ("first" or "last" insert, "final" emit): the device
-    counterpart of `join_window` with an `EventClock`, a
-    `TumblingWindower` and ``ordered=True``.
+    """Two-sided join over tumbling or sliding event-time windows of
+    columnar batches on GPU ("first" or "last" insert, "final" emit):
+    the device counterpart of `join_window` with an `EventClock`, a
+    `TumblingWindower` or `SlidingWindower` and ``ordered=True``.
 
     An event ``(key, ts, val)`` of either side belongs to window
     ``(ts - align_to) // length``, and each (key, window) keeps one
@@ -1228,6 +1230,22 @@ def window_join(
     0 says the left side is present, bit 1 the right; a missing side's
     value column reads 0 (values are arbitrary int64, so only the mask
     tells).  At EOF every remaining cell is emitted.
+
+    With `offset` shorter than `length` the windows slide: one opens
+    every `offset` and each lasts `length`, as `SlidingWindower`'s do,
+    and an event belongs to every window that covers it.  `wins` then
+    counts `offset` strides: a row's window starts at ``align_to +
+    wins * offset`` and ends `length` later, and ids below zero are
+    windows that opened before `align_to`.  Events are inserted once
+    into panes of ``gcd(length, offset)`` and a close folds the panes
+    of each due window (see `SlidingWindowJoinState`), so an insert
+    costs what a tumbling join of that pane width costs.  At most 64
+    panes per window (``length / gcd(length, offset) <= 64``).  Size
+    `slots_pow` for keys x (panes per window + panes the wait spans),
+    and `fold_slots_pow` (the fold table, `slots_pow` by default) for
+    the (key, window) rows of one close, under half full: about
+    ``2 x keys`` when one window closes at a time.  With no `offset`,
+    or ``offset == length``, the windows tumble exactly as before.
 
     A window close reclaims the closed cells, so the stream may run
     unbounded: size `slots_pow` (2^slots_pow table slots, best kept
@@ -1249,8 +1267,10 @@ def window_join(
     Raises `ValueError` at build time for an `emit_mode` other than
     ``"final"`` ("complete" and "running" depend on the order of single
     events across the sides) and for an `insert_mode` other than
-    ``"first"`` or ``"last"`` ("product" included); only two sides and
-    tumbling windows exist here.  Raises `NotImplementedError` for
+    ``"first"`` or ``"last"`` ("product" included), for an `offset`
+    that is not positive or is longer than `length`, and for more than
+    64 panes per window; only two sides exist here.  Raises
+    `NotImplementedError` for
     ``exchange=True`` or a process group of more than one rank.
     Raises `RuntimeError` when the table overflows or one close has
     more than `out_cap` rows; neither ever returns short output.
@@ -1258,7 +1278,11 @@ def window_join(
     import torch
     import torch.distributed as dist
 
-    from .state import WindowJoinState
+    from .state import (
+        SlidingWindowJoinState,
+        WindowJoinState,
+        _sliding_join_geometry,
+    )
     from . import _ms as to_ms
 
     if emit_mode != "final":
@@ -1292,13 +1316,26 @@ def window_join(
     if len_ms <= 0:
         msg = "window_join length must be positive"
         raise ValueError(msg)
+    off_ms = None if offset is None else int(offset.total_seconds() * 1000)
+    if off_ms == len_ms:
+        off_ms = None
+    if off_ms is not None:
+        _sliding_join_geometry(len_ms, off_ms)
 
     def shim_builder(resume_state):
-        state = WindowJoinState(
-            torch.device(device), align_ms, len_ms,
-            insert_mode=insert_mode, slots_pow=slots_pow,
-            out_cap=out_cap, wait_ms=wait_ms,
-        )
+        if off_ms is None:
+            state = WindowJoinState(
+                torch.device(device), align_ms, len_ms,
+                insert_mode=insert_mode, slots_pow=slots_pow,
+                out_cap=out_cap, wait_ms=wait_ms,
+            )
+        else:
+            state = SlidingWindowJoinState(
+                torch.device(device), align_ms, len_ms, off_ms,
+                insert_mode=insert_mode, slots_pow=slots_pow,
+                out_cap=out_cap, wait_ms=wait_ms,
+                fold_slots_pow=fold_slots_pow,
+            )
         return _DeviceWindowJoinLogic(state, wait_ms, resume_state)
 
     shard = "shard-0"

@@ -9,7 +9,9 @@ Device twins of `reduce_final`-style keyed aggregations and the
   open-address state, "last" insert / "complete" emit (config 4);
 - :class:`WindowJoinState` — the same join per tumbling event-time
   window, "first" or "last" insert / "final" emit, with a close that
-  reclaims the closed cells.
+  reclaims the closed cells;
+- :class:`SlidingWindowJoinState` — that join over sliding windows:
+  one insert per event into panes, folded per window at close.
 
 All support pinned-host snapshot spill for recovery and have CPU
 twins for GPU-less test runs.
@@ -1660,6 +1662,7 @@ class WindowJoinState:
         taken without restores into either kind."""
         import torch
 
+        self._check_kind(snap)
         theirs = (
             snap.get("align_ms"), snap.get("len_ms"), snap.get("insert_mode")
         )
@@ -1693,6 +1696,324 @@ class WindowJoinState:
                 )
         self.max_ts_host = snap["max_ts"]
         self.closed_horizon = snap["closed_horizon"]
+
+    def _check_kind(self, snap: Dict[str, Any]) -> None:
+        """Refuse a snapshot of the other window kind: the cells of a
+        sliding join are panes, and its window horizon would be lost."""
+        if "win_len_ms" in snap:
+            geom = (snap.get("win_len_ms"), snap.get("off_ms"))
+            msg = (
+                f"snapshot of a sliding window join (length, offset) = "
+                f"{geom} ms cannot restore a tumbling window join"
+            )
+            raise ValueError(msg)
+
+
+def _sliding_join_geometry(len_ms: int, off_ms: int) -> Tuple[int, int, int]:
+    """Pane width and panes per window and per offset of a sliding
+    join, or the `ValueError` of a geometry it does not support."""
+    import math
+
+    if off_ms <= 0:
+        msg = "sliding window join `off_ms` must be positive"
+        raise ValueError(msg)
+    if off_ms > len_ms:
+        msg = (
+            "sliding window join `off_ms` can't be longer than `len_ms`; "
+            "there would be gaps between windows"
+        )
+        raise ValueError(msg)
+    g = math.gcd(len_ms, off_ms)
+    if len_ms // g > SlidingWindowJoinState.MAX_PANES:
+        msg = (
+            f"sliding window join of {len_ms} ms every {off_ms} ms "
+            f"needs {len_ms // g} panes of {g} ms per window; at "
+            f"most {SlidingWindowJoinState.MAX_PANES} are supported"
+        )
+        raise ValueError(msg)
+    return g, len_ms // g, off_ms // g
+
+
+class SlidingWindowJoinState(WindowJoinState):
+    """Two-sided "first"/"last" join over sliding event-time windows on
+    device, "final" emit (the device twin of the host `join_window`
+    with an `EventClock`, a `SlidingWindower` and ``ordered=True``).
+
+    Window `w` spans ``[align + w * off, align + w * off + len)``, the
+    ids of `SlidingWindower`.  Events are inserted once, by the
+    parent's three insert kernels, into non-overlapping *panes* of
+    width ``g = gcd(len_ms, off_ms)``: the table holds (key, pane)
+    cells and an insert costs what a tumbling join of length `g`
+    costs.  A window is the ``L = len_ms / g`` panes
+    ``[w * o, w * o + L)`` with ``o = off_ms / g``.  The panes of a
+    window are disjoint in time, so the winner of a side over the
+    window is the winner of the pane with the greatest ("last") or
+    smallest ("first") stamp; a close folds the panes of every due
+    window that way into a separate fold table (k_wjoin_pane_stamp,
+    k_wjoin_pane_commit), reads the rows out of it and drops the panes
+    that no open window contains.
+
+    `insert`, `take_late`, `late_drained`, `extract`,
+    `snapshot_to_host` and `restore_from_host` work on pane cells (the
+    parent's `len_ms` is `g` and its `closed_horizon` the pane floor);
+    the closing calls return windows.  Late tracking is the parent's,
+    unchanged: an accepted event has ``ts >= watermark - wait``, and
+    window `w` is closed only when ``align + w * off + len <=
+    watermark - wait``, so an accepted event lies in no emitted window.
+
+    A pane outlives the windows that have closed over it for as long
+    as an open window contains it, so pane cells alone do not say
+    which windows are still owed: `win_horizon` travels with them in
+    snapshots.
+
+    Limits:
+
+    - ``L <= 64``.  The table holds up to `L` live cells per key, so
+      size `slots_pow` for ``keys x (L + panes the wait spans)``.
+    - The fold table (`fold_slots_pow`, the table's size by default)
+      has to hold the (key, window) rows of one close, kept under half
+      full.  Reading the rows out and refilling it costs time in
+      proportion to its size, so a stream that closes one window per
+      close does best with a fold table sized for ``2 x keys``.
+    - Event times must not precede `align_ms` (a window below
+      ``1 - L`` is not built), and pane ids ``(t - align_ms) / g``
+      must fit in int32.
+    """
+
+    MAX_PANES = 64
+
+    def __init__(
+        self,
+        device,
+        align_ms: int,
+        len_ms: int,
+        off_ms: int,
+        insert_mode: str = "last",
+        slots_pow: int = 20,
+        out_cap: int = 1 << 20,
+        wait_ms: int = 0,
+        track_late: bool = False,
+        late_cap: int = 0,
+        fold_slots_pow: Optional[int] = None,
+    ):
+        g, n_w, n_o = _sliding_join_geometry(len_ms, off_ms)
+        super().__init__(
+            device, align_ms, g, insert_mode=insert_mode,
+            slots_pow=slots_pow, out_cap=out_cap, wait_ms=wait_ms,
+            track_late=track_late, late_cap=late_cap,
+        )
+        self.win_len_ms = len_ms
+        self.off_ms = off_ms
+        self.panes_per_window = n_w
+        self.panes_per_offset = n_o
+        #: Windows below this id have been emitted.
+        self.win_horizon = -(1 << 62)
+        #: The fold table (keys, ts0, ts1, v0, v1); None until a close
+        #: has a pane to fold or drop.
+        self.fold: Optional[Tuple[Any, ...]] = None
+        #: Most blocks the two close passes launch (0: the launcher's
+        #: cap); fewer blocks than 2,048-slot chunks makes each block
+        #: stride over several.
+        self.close_blocks = 0
+        if not self.cpu:
+            self.fold_slots = (
+                self.nslots if fold_slots_pow is None else 1 << fold_slots_pow
+            )
+
+    def horizon_for(
+        self, watermark_ms: int, wait_ms: Optional[int] = None
+    ) -> int:
+        """Window `w` is due once ``w * off + len`` is at or below the
+        watermark minus `wait_ms`; the windows below the returned id
+        are."""
+        if wait_ms is None:
+            wait_ms = self.wait_ms
+        rel = watermark_ms - wait_ms - self.align_ms
+        return (rel - self.win_len_ms) // self.off_ms + 1
+
+    def close_below(self, horizon: int) -> Optional[Dict[str, Any]]:
+        """Return the windows in [win_horizon, horizon), folded from
+        their panes, forget the panes that lie in no window at or above
+        `horizon`, and advance `win_horizon` to `horizon` and the pane
+        floor `closed_horizon` to ``horizon * o``.
+
+        On device two launches fold and migrate (k_wjoin_pane_stamp,
+        k_wjoin_pane_commit); the rows are then extracted from the fold
+        table, which is refilled for the next close, all on the one
+        stream.  The fold table and the second pane table are allocated
+        by the first close that has a pane to fold or drop."""
+        if horizon <= self.win_horizon:
+            return None
+        win_hi = min(horizon, 1 << 40)
+        pane_keep = win_hi * self.panes_per_offset
+        out = self._fold(win_hi, pane_keep)
+        self.win_horizon = horizon
+        self.closed_horizon = pane_keep
+        return out
+
+    def _fold(self, win_hi: int, pane_keep: int) -> Optional[Dict[str, Any]]:
+        """The rows of the windows in [win_horizon, win_hi); panes
+        below `pane_keep` are forgotten.  Moves no horizon."""
+        n_w, n_o = self.panes_per_window, self.panes_per_offset
+        win_lo = max(self.win_horizon, -(1 << 39))
+        if self.cpu:
+            # Per (key, window) and side the pane with the greatest
+            # ("last") / smallest ("first") stamp; stamps of different
+            # panes never tie.
+            folded: Dict[Tuple[int, int], List[Optional[int]]] = {}
+            for (k, p), c in self._table.items():
+                w_first = max((p - n_w) // n_o + 1, win_lo, 1 - n_w)
+                w_last = min(p // n_o, win_hi - 1)
+                for w in range(w_first, w_last + 1):
+                    cur = folded.setdefault((k, w), [None, None, None, None])
+                    for j in (0, 2):
+                        t = c[j]
+                        if t is None:
+                            continue
+                        if cur[j] is None or (
+                            t < cur[j] if self.first else t > cur[j]
+                        ):
+                            cur[j] = t
+                            cur[j + 1] = c[j + 1]
+            for kp in [kp for kp in self._table if kp[1] < pane_keep]:
+                del self._table[kp]
+            return _wjoin_rows([(k, w, c) for (k, w), c in folded.items()])
+        if self.tables_alt is None:
+            # A pane lies in a window below `win_hi` iff it is below
+            # (win_hi - 1) * o + L, and a pane is dropped iff it is
+            # below `pane_keep`: with no pane under the larger of the
+            # two there is nothing to fold or to drop.
+            bound = max((win_hi - 1) * n_o + n_w, pane_keep)
+            if not self._any_pane_below(bound):
+                return None
+            self.tables_alt = self._new_table()
+        if self.fold is None:
+            import torch
+
+            self.fold = tuple(
+                torch.full(
+                    (self.fold_slots,), fill, dtype=torch.int64,
+                    device=self.device,
+                )
+                for fill in self._fills[:5]
+            )
+        live = (
+            self.tkeys, self.tts0, self.tts1, self.tv0, self.tv1,
+            self.telect,
+        )
+        self.k.wjoin_pane_stamp(
+            *live[:5],
+            *self.tables_alt[:5],
+            *self.fold,
+            win_lo,
+            win_hi,
+            pane_keep,
+            n_w,
+            n_o,
+            self.first,
+            self.error_flag,
+            self.close_blocks,
+        )
+        # The old pane table is still intact: the commit reads it.
+        self.k.wjoin_pane_commit(
+            *live[:5],
+            *self.fold,
+            win_lo,
+            win_hi,
+            n_w,
+            n_o,
+            self.first,
+            self.error_flag,
+            self.close_blocks,
+        )
+        (
+            self.tkeys, self.tts0, self.tts1, self.tv0, self.tv1,
+            self.telect,
+        ) = self.tables_alt
+        self.tables_alt = live
+        # Election words are idle between inserts (see close_below of
+        # the parent).
+        for t, fill in zip(live[:5], self._fills):
+            t.fill_(fill)
+        # Every fold cell with a side is a row; its window column holds
+        # w + L (see the kernel).
+        self.out_n.zero_()
+        self.k.wjoin_extract(
+            *self.fold,
+            0,
+            1 << 40,
+            self.ts_none,
+            *(self.out[c] for c in ("keys", "wins", "v0", "v1", "t0", "t1")),
+            self.out["mask"],
+            self.out_n,
+        )
+        for t, fill in zip(self.fold, self._fills):
+            t.fill_(fill)
+        n = int(self.out_n.item())
+        self._check(n)
+        if n == 0:
+            return None
+        out = self._take(n, _WJOIN_COLS)
+        out["wins"] -= n_w
+        return out
+
+    def _any_pane_below(self, bound: int) -> bool:
+        """Whether the table holds a pane in [closed_horizon, bound).
+        `k_wjoin_extract` counts the rows past the buffers' capacity
+        without writing them, so the count alone is read."""
+        self.out_n.zero_()
+        self.k.wjoin_extract(
+            self.tkeys, self.tts0, self.tts1, self.tv0, self.tv1,
+            self._win_lo(), bound, self.ts_none,
+            *(self.out[c] for c in ("keys", "wins", "v0", "v1", "t0", "t1")),
+            self.out["mask"], self.out_n,
+        )
+        return int(self.out_n.item()) > 0
+
+    def close_all(self) -> Optional[Dict[str, Any]]:
+        """Every window that still holds a pane, the unfinished ones
+        included; :meth:`close_below` with an unbounded horizon.  The
+        state takes no further input afterwards."""
+        return self.close_below(1 << 40)
+
+    def close_eof(self) -> Optional[Dict[str, Any]]:
+        """End of input, as the operator closes it: the rows of every
+        window at or above `win_horizon`, the unfinished ones included,
+        with both horizons and every live pane left where they are.  A
+        snapshot taken afterwards resumes exactly: an execution that
+        continues the stream emits the windows that were unfinished
+        here again, complete, when they fall due."""
+        return self._fold(1 << 40, self.closed_horizon)
+
+    def snapshot_to_host(self) -> Dict[str, Any]:
+        out = super().snapshot_to_host()
+        out["win_horizon"] = self.win_horizon
+        out["win_len_ms"] = self.win_len_ms
+        out["off_ms"] = self.off_ms
+        return out
+
+    def _check_kind(self, snap: Dict[str, Any]) -> None:
+        if "win_len_ms" not in snap:
+            msg = (
+                "snapshot of a tumbling window join cannot restore a "
+                "sliding window join"
+            )
+            raise ValueError(msg)
+        geom = (snap.get("win_len_ms"), snap.get("off_ms"))
+        if geom != (self.win_len_ms, self.off_ms):
+            msg = (
+                f"snapshot of a sliding window join (length, offset) = "
+                f"{geom} ms cannot restore a state of "
+                f"{(self.win_len_ms, self.off_ms)} ms"
+            )
+            raise ValueError(msg)
+
+    def restore_from_host(self, snap: Dict[str, Any]) -> None:
+        """The parent's restore of the pane cells, then the window
+        horizon.  A snapshot of another (length, offset), or of a
+        tumbling join, is refused."""
+        super().restore_from_host(snap)
+        self.win_horizon = snap["win_horizon"]
 
 
 class SessionAggState:
