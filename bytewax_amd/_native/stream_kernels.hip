@@ -751,6 +751,34 @@ __host__ __device__ __forceinline__ uint64_t mixn_inv(uint64_t y, int n) {
   return y;
 }
 
+// mixn on the 32-bit halves of x = hi << 32 | lo, in place: the same
+// value as mixn(x, n) for 33 <= n <= 56 (MIXN_PAIR_MIN_N, _MAX_N) and
+// hi < 2^(n-32).  With s = ceil(n/2) in 17..28:
+//   - x >> s is below 2^32 (n - s <= 32), so an xor-shift changes only
+//     `lo`, by the low word of the pair shifted right (one alignbit);
+//   - of the high word of x * C only the low n - 32 <= 24 bits survive
+//     the mask, and the low 24 bits of a product depend only on the low
+//     24 bits of its factors, so the two cross terms are 24-bit
+//     multiplies and one 32x32 -> 64 multiply per round is left.
+#define MIXN_PAIR_MIN_N 33
+#define MIXN_PAIR_MAX_N 56
+
+__device__ __forceinline__ void mixn_pair(uint32_t& lo, uint32_t& hi, int n) {
+  const uint32_t hm = (1u << (n - 32)) - 1u;
+  const uint32_t s = (uint32_t)(n + 1) >> 1;
+  auto round = [&](uint64_t c) {
+    lo ^= __builtin_amdgcn_alignbit(hi, lo, s);
+    const uint64_t p = (uint64_t)lo * (uint32_t)c;
+    hi = ((uint32_t)(p >> 32) + __umul24(lo, (uint32_t)(c >> 32)) +
+          __umul24(hi, (uint32_t)c)) & hm;
+    lo = (uint32_t)p;
+  };
+  round(MIXN_C1);
+  round(MIXN_C2);
+  round(MIXN_C3);
+  lo ^= __builtin_amdgcn_alignbit(hi, lo, s);
+}
+
 // Classic `packed` of the compact entry `e` of segment `seg`, against
 // the entry base whose low 32 bits are `wbase`.
 __device__ __forceinline__ uint64_t compact_classic(
@@ -1526,7 +1554,16 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_staged2(
 // segment index in gdst (GDC_SPILL | segment) so that P4 can rebuild
 // classic `packed`, and the final flush knows its segment anyway.
 // `dbits` is D; the host guarantees 2^(D+1) segments.
+//
+// A lane holds four consecutive events at a time: slot u = 4q + j of
+// lane `tid` is event (q * BLK + tid) * 4 + j of the tile.  (Entries
+// inside a segment are in atomic-arrival order anyway, and the
+// aggregation counts.)  A full tile loads each column with U/4 loads of
+// 16 bytes when VEC says both column pointers are 16-byte aligned, with
+// unclamped dwords otherwise; the last, partial tile loads clamped
+// dwords under the same mapping.
 #define SCC_GRAN 16
+typedef int32_t scc_i32x4 __attribute__((ext_vector_type(4)));
 #define GDC_SPILL 0x80000000u
 
 static inline size_t compact_lds_bytes(int64_t nseg, int64_t tile) {
@@ -1537,7 +1574,7 @@ static inline size_t compact_lds_bytes(int64_t nseg, int64_t tile) {
          + (stage_n / SCC_GRAN) * sizeof(uint32_t);  // gdst
 }
 
-template <int U = 16, int BLK = 512>
+template <int U = 16, int BLK = 512, bool VEC = true>
 __global__ __launch_bounds__(BLK) void k_radix_scatter_compact(
     const int32_t* __restrict__ keys,
     const int32_t* __restrict__ ts,
@@ -1563,6 +1600,7 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_compact(
   static_assert(T + (SCC_GRAN - 1) * BLK < (1 << 14),
                 "staging offset must fit 14 bits");
   static_assert(T <= (1 << 13), "tile rank shares a word with the segment");
+  static_assert(U % 4 == 0, "four consecutive events per lane");
   extern __shared__ __attribute__((aligned(16))) char smem_cc[];
   __shared__ int s_wtot[NW];
   const int nseg = 2 << dbits;  // host: nseg <= BLK
@@ -1592,62 +1630,92 @@ __global__ __launch_bounds__(BLK) void k_radix_scatter_compact(
     else atomicOr(error_flag, 1);
   };
 
-  // Raw columns of one tile, loaded a tile ahead, without a branch (see
-  // k_radix_scatter_staged2).
-  int32_t rk[U];
-  int32_t rt[U];
+  // Raw columns of one tile, loaded a tile ahead and held as the
+  // 16-byte vectors they arrive in (slot u is rk[u / 4][u % 4]).
+  // Whether the tile is full is uniform across the block.
+  scc_i32x4 rk[U / 4];
+  scc_i32x4 rt[U / 4];
   auto load_tile = [&](int64_t t0) {
+    if (t0 + T <= n) {
+      const int32_t* kp = keys + t0 + 4 * tid;
+      const int32_t* tp = ts + t0 + 4 * tid;
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      int64_t i = t0 + u * BLK + tid;
-      if (i > n - 1) i = n - 1;
-      rk[u] = keys[i];
-      rt[u] = ts[i];
+      for (int q = 0; q < U / 4; ++q) {
+        if (VEC) {
+          rk[q] = *(const scc_i32x4*)(kp + q * BLK * 4);
+          rt[q] = *(const scc_i32x4*)(tp + q * BLK * 4);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            rk[q][j] = kp[q * BLK * 4 + j];
+            rt[q][j] = tp[q * BLK * 4 + j];
+          }
+        }
+      }
+    } else {
+      const int last = (int)(n - 1 - t0);  // 0 <= last < T - 1
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        int e = ((u >> 2) * BLK + tid) * 4 + (u & 3);
+        if (e > last) e = last;
+        rk[u >> 2][u & 3] = keys[t0 + e];
+        rt[u >> 2][u & 3] = ts[t0 + e];
+      }
     }
   };
   const int64_t stride = (int64_t)gridDim.x * T;
   // Maximum of the int32 deltas (the base is added once at the end),
-  // starting from the lane's first event when it has one.
+  // starting from the lane's first slot.  A slot past the end of the
+  // batch holds a copy of the batch's last event (the clamped load),
+  // which cannot raise the batch's maximum, so every slot of a block
+  // that has a tile takes part and no `in` test is needed.
   int64_t local_max = 0;
   int64_t t0 = (int64_t)blockIdx.x * T;
-  const bool seen = t0 + tid < n;
+  const bool seen = t0 < n;
   if (t0 < n) {
     load_tile(t0);
-    local_max = (int64_t)rt[0];
+    local_max = (int64_t)rt[0][0];
   }
   for (; t0 < n; t0 += stride) {
     uint32_t pk[U];
     int sr[U];  // (rank << 13) | segment, or -1 when not placed
-    // P1: classify, rank.  Events of this tile that lane `tid` holds,
-    // in steps of BLK.
-    int64_t left64 = n - t0 - tid;
-    const int left = left64 > T ? T : (left64 < 0 ? 0 : (int)left64);
+    // P1: classify, rank.  Slot u holds an event of this tile when its
+    // offset from the lane's first event lies below `left`.
+    const int64_t rem = n - t0;
+    const int left = (rem > T ? T : (int)rem) - 4 * tid;
     int32_t dmax = (int32_t)local_max;
     uint32_t rare = 0;  // events for the generic path
     // Unconditional histogram atomics, one batch (see staged2).
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const bool in = u * BLK < left;
-      const uint32_t d = (uint32_t)rt[u];
+      const bool in = (u >> 2) * BLK * 4 + (u & 3) < left;
+      const uint32_t d = (uint32_t)rt[u >> 2][u & 3];
       const uint32_t q = win32_div(d + w32.c, w32);
       const uint32_t delta = q - w32.qoff;
       const bool fits = d - w32.dlo < w32.dspan && delta < dlimit;
-      const uint64_t y = mixn(
-          ((uint64_t)(delta & (dlimit - 1)) << 32) | (uint32_t)rk[u], nbits);
-      pk[u] = (uint32_t)y & 0x7FFFFFFFu;
+      uint32_t lo = (uint32_t)rk[u >> 2][u & 3];
+      uint32_t hi = delta & (dlimit - 1);
+      mixn_pair(lo, hi, nbits);
+      pk[u] = lo & 0x7FFFFFFFu;
       if (in && !fits) rare |= 1u << u;
-      if (in && (int32_t)d > dmax) dmax = (int32_t)d;
+      if ((int32_t)d > dmax) dmax = (int32_t)d;
+      // `ok` is spent before the atomics return: all ones in place of
+      // the segment make the whole word -1.  The empty asm keeps the
+      // compiler from turning that back into a select on `ok`, which
+      // would hold a lane mask per slot across the batch of atomics.
       const bool ok = in && fits;
-      int b = (int)(y >> 31);  // < 2^(dbits+1) = nseg
+      int b = (int)((hi << 1) | (lo >> 31));  // < 2^(dbits+1) = nseg
+      int bm = ok ? b : -1;
+      asm("" : "+v"(bm));
       int rank = atomicAdd(&lhist[b], ok ? 1 : 0);
-      sr[u] = ok ? ((rank << 13) | b) : -1;
+      sr[u] = (rank << 13) | bm;
     }
     local_max = dmax;
     // Rare: one copy of the generic window code, columns read again.
     while (rare != 0) {
       int u = __ffs(rare) - 1;
       rare &= rare - 1;
-      int64_t i = t0 + u * BLK + tid;
+      int64_t i = t0 + ((u >> 2) * BLK + tid) * 4 + (u & 3);
       int64_t win = win_of((int64_t)ts[i] + ts_base, align_ms, len_ms,
                            win_m2, win_maxfast);
       spill(((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)keys[i]);
@@ -5169,9 +5237,12 @@ static void launch_count_staged(
   if (count_staged2_ok(xf, evp, nseg)) {
     // 512 x 16: one workgroup per CU (LDS-bound), 8192-event tiles.
     // 1024 x 8 keeps 16 waves per CU and measured 4 % faster alone
-    // (325 against 338 us), but its 128-VGPR budget spills 12 bytes
-    // per lane (36 with int64 timestamps) once the next tile's columns
-    // are held in registers; 512 x 16 has 256 and no scratch.
+    // for staged2 before the next tile's columns were held in
+    // registers (325 against 338 us); with them its 128-VGPR budget
+    // spills 12 bytes per lane (36 with int64 timestamps), and the
+    // compact kernel at 1024 x 8 spills 172 (it needs 234 VGPRs at
+    // 512 x 16, where the budget is 256 and nothing spills).  The
+    // hashed and the compact kernels are built at 512 x 16 only.
     // One block per CU, each walking its share of the tiles: measured
     // fastest when the scatter has the chip to itself (1024 x 8: 325
     // us at 256 blocks, 351 at 512, 407 at 1024 for the 64M-event
@@ -5192,17 +5263,27 @@ static void launch_count_staged(
         if (ce.compact()) {
           TORCH_CHECK(nseg == ((int64_t)2 << ce.dbits) && nseg <= 512,
                       "compact entries planned for another segment count");
+          TORCH_CHECK(32 + ce.dbits >= MIXN_PAIR_MIN_N &&
+                          32 + ce.dbits <= MIXN_PAIR_MAX_N,
+                      "compact entries: hash width outside mixn_pair's range");
           int64_t gs = (n + 8191) / 8192;
           unsigned cap_gs = env_blocks > 0 ? (unsigned)env_blocks : cus;
           if (gs > (int64_t)cap_gs) gs = cap_gs;
           if (gs < 1) gs = 1;
-          // Granules of 16 entries: both launches round `cap` down.
-          hipLaunchKernelGGL(
-              (k_radix_scatter_compact<16, 512>), dim3((unsigned)gs),
-              dim3(512), compact_lds_bytes(nseg, 8192), stream, keys, ts, n,
-              align_ms, len_ms, ts_base, ce.dbits,
-              cap & ~(int64_t)(SCC_GRAN - 1), gcur, (uint32_t*)evp, ovc, ovp,
-              ov_cap, max_ts, err, win_m2, win_maxfast, w32);
+          // 16-byte column loads need both columns 16-byte aligned; a
+          // per-source-rank segment of a receive buffer need not be.
+          const bool vec = (((uintptr_t)keys | (uintptr_t)ts) & 15) == 0;
+          auto launch = [&](auto kern) {
+            // Granules of 16 entries: both launches round `cap` down.
+            hipLaunchKernelGGL(
+                kern, dim3((unsigned)gs), dim3(512),
+                compact_lds_bytes(nseg, 8192), stream, keys, ts, n, align_ms,
+                len_ms, ts_base, ce.dbits, cap & ~(int64_t)(SCC_GRAN - 1),
+                gcur, (uint32_t*)evp, ovc, ovp, ov_cap, max_ts, err, win_m2,
+                win_maxfast, w32);
+          };
+          if (vec) launch(k_radix_scatter_compact<16, 512, true>);
+          else launch(k_radix_scatter_compact<16, 512, false>);
           HIP_CHECK(hipGetLastError());
           return;
         }
