@@ -4053,6 +4053,291 @@ __global__ __launch_bounds__(CM_BLK) void k_wjoin_pane_commit(
 }
 
 // ---------------------------------------------------------------------------
+// Windowed product join: every left value of a (key, window) cell
+// paired with every right value of it ("product" insert, "final" emit).
+// A cell is two variable-length value lists, so the state is not a row
+// per cell but
+//   table   `tkeys` holds `window << 32 | key` (EMPTY_SLOT = empty) and
+//           `tcnt[2 * slot + s]` the number of values of side `s`;
+//   logs    one append log per side of 16-byte entries (packed cell
+//           word, int64 value), `log_n` its int32 cursor.
+// The table says how many values a cell has, the logs hold them in
+// arrival order of the reservations, which is no order at all: the
+// product of two lists is the same multiset whatever their order.
+//
+// Insert (k_wjprod_insert, one launch per side batch) is wjprod_put
+// per event: find_slot, atomicAdd on the side's count, one 16-byte
+// append at a wave-reserved log position.  An event that finds the
+// table full sets the error flag and does neither, so for every
+// (cell, side) the count equals the number of log entries at all times
+// between launches (*).
+//
+// A close at [win_lo, win_hi) is three launches around one readback:
+//   plan    (k_wjprod_plan) lists every due cell as (packed, n0, n1)
+//           and writes its list index into `slot_cell[slot]`.  Nothing
+//           else is written, so the host may still refuse the close
+//           (too many rows) with the state untouched.  The host takes
+//           inclusive int64 prefix sums of n0 + n1 (`val_end`) and of
+//           max(n0, 1) * max(n1, 1) (`row_end`) over the list.
+//   gather  (k_wjprod_gather, once per side over its log) sorts every
+//           entry by its window `w`: w < win_lo is dropped (an event
+//           behind the closed horizon); w < win_hi stores its value
+//           into the arena; otherwise it is put into the fresh table
+//           and the fresh log by wjprod_put.  The caller swaps tables
+//           and logs and resets the retired ones.
+//   expand  (k_wjprod_expand) one thread per output row.
+//
+// Exactness.  (1) Every log entry takes exactly one of the three arms
+// of the gather, by its window alone.  (2) Arena: cell `c` owns the
+// words [val_end[c] - n0 - n1, val_end[c]), disjoint between cells by
+// the prefix sum; side 0 the first n0 of them, side 1 the rest.  A due
+// entry of (cell, side) takes `atomicSub(count, 1) - 1` as its place.
+// By (*) exactly n_s entries of that (cell, side) exist, the count
+// starts at n_s (the plan only read it), and atomics on one address
+// are totally ordered, so the places handed out are a permutation of
+// 0 .. n_s - 1: every arena word is written exactly once.  (3) A
+// migrated entry bumps the fresh count and appends to the fresh log
+// together, so (*) holds for the fresh state.  The fresh log has the
+// retired one's capacity and receives a subset of its entries.  (4) The
+// insert, the three close launches, the prefix sums, the resets and
+// the log growth copies are all enqueued on one stream.
+#define ERR_WJPROD_BOUND 4  // a guard fired: host-side bound is wrong
+
+// One event into a product-join table and log.  Called by every lane
+// still in its loop, `take` or not, so that the wave votes together.
+__device__ __forceinline__ void wjprod_put(
+    bool take, uint64_t packed, int64_t val,
+    uint64_t* __restrict__ tkeys, int* __restrict__ tcnt, uint64_t mask,
+    int side, ulonglong2* __restrict__ log, int* __restrict__ log_n,
+    int64_t log_cap, int* __restrict__ error_flag) {
+  uint64_t slot = take ? find_slot(tkeys, mask, packed) : ~0ULL;
+  const bool ok = slot != ~0ULL;
+  if (take && !ok) atomicOr(error_flag, 1);
+  if (ok) atomicAdd(&tcnt[2 * slot + side], 1);
+  int pos = wave_reserve(ok, log_n);
+  if (ok) {
+    if (pos >= 0 && pos < log_cap) {
+      log[pos] = make_ulonglong2(packed, (unsigned long long)val);
+    } else {
+      atomicOr(error_flag, ERR_WJPROD_BOUND);
+    }
+  }
+}
+
+template <typename TS = int64_t>
+__global__ void k_wjprod_insert(
+    const int32_t* __restrict__ keys,
+    const TS* __restrict__ ts,
+    const int64_t* __restrict__ vals,
+    int64_t n,
+    uint64_t* __restrict__ tkeys,
+    int* __restrict__ tcnt,
+    uint64_t mask,
+    int side,
+    ulonglong2* __restrict__ log,
+    int* __restrict__ log_n,
+    int64_t log_cap,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base,
+    unsigned long long* __restrict__ max_ts,
+    int* __restrict__ error_flag) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  int64_t local_max = 0;
+  for (; i < n; i += stride) {
+    int64_t t = (int64_t)ts[i] + ts_base;
+    if (t > local_max) local_max = t;
+    int64_t win = floor_div(t - align_ms, len_ms);
+    uint64_t packed =
+        ((uint64_t)(uint32_t)(int32_t)win << 32) | (uint32_t)keys[i];
+    wjprod_put(true, packed, vals[i], tkeys, tcnt, mask, side, log, log_n,
+               log_cap, error_flag);
+  }
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    int64_t other = __shfl_down((long long)local_max, off);
+    if (other > local_max) local_max = other;
+  }
+  if ((threadIdx.x & (WAVE - 1)) == 0 && local_max > 0) {
+    atomicMax(max_ts, (unsigned long long)local_max);
+  }
+}
+
+// The plan pass of the product-join close (see above): the due cells
+// of [win_lo, win_hi) as a compact list, in the chunked shape of
+// k_wjoin_close_migrate.  List places are reserved once per chunk; a
+// slot is listed at most once, so `cells_n` never passes `nslots`, the
+// length of the list arrays.  Reads the table, writes the list, its
+// cursor and `slot_cell` at the listed slots only.
+__global__ __launch_bounds__(CM_BLK) void k_wjprod_plan(
+    const uint64_t* __restrict__ tkeys,
+    const int* __restrict__ tcnt,
+    int64_t nslots,
+    int64_t win_lo,
+    int64_t win_hi,
+    uint64_t* __restrict__ cell_pk,
+    int* __restrict__ cell_n,  // (n0, n1) per listed cell
+    int* __restrict__ slot_cell,
+    int* __restrict__ cells_n) {
+  constexpr int NW = CM_BLK / WAVE;
+  // Double-buffered by chunk parity: two barriers per chunk suffice.
+  __shared__ int s_wave[2][NW];
+  __shared__ int s_base[2];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const bool vec = (((uintptr_t)tkeys) & 15) == 0;
+  const int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  int par = 0;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x, par ^= 1) {
+    // Slot of k[q]: s0 + (q / 2) * (CM_BLK * 2) + (q & 1).
+    const int64_t s0 = c * CM_CHUNK + threadIdx.x * 2;
+    uint64_t k[CM_PER];
+    for (int j = 0; j < CM_PER / 2; ++j) {
+      int64_t s = s0 + (int64_t)j * (CM_BLK * 2);
+      if (vec && s + 1 < nslots) {
+        ulonglong2 kk = *(const ulonglong2*)(tkeys + s);
+        k[2 * j] = kk.x;
+        k[2 * j + 1] = kk.y;
+      } else {
+        for (int q = 0; q < 2; ++q) {
+          k[2 * j + q] = s + q < nslots ? tkeys[s + q] : EMPTY_SLOT;
+        }
+      }
+    }
+    unsigned takem = 0;
+    for (int q = 0; q < CM_PER; ++q) {
+      if (k[q] == EMPTY_SLOT) continue;
+      int64_t win = (int64_t)(int32_t)(uint32_t)(k[q] >> 32);
+      if (win >= win_lo && win < win_hi) takem |= 1u << q;
+    }
+    const int cnt = __popc(takem);
+    int incl = cnt;
+    for (int off = 1; off < WAVE; off <<= 1) {
+      int o = __shfl_up(incl, off);
+      if (lane >= off) incl += o;
+    }
+    if (lane == WAVE - 1) s_wave[par][wave] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int total = 0;
+      for (int w = 0; w < NW; ++w) total += s_wave[par][w];
+      s_base[par] = total > 0 ? atomicAdd(cells_n, total) : 0;
+    }
+    __syncthreads();
+    if (takem != 0) {
+      int64_t idx = (int64_t)s_base[par] + (incl - cnt);
+      for (int w = 0; w < wave; ++w) idx += s_wave[par][w];
+      for (int q = 0; q < CM_PER; ++q) {
+        if (!((takem >> q) & 1u)) continue;
+        if (idx < nslots) {
+          int64_t s = s0 + (int64_t)(q >> 1) * (CM_BLK * 2) + (q & 1);
+          int2 nn = *(const int2*)(tcnt + 2 * s);
+          cell_pk[idx] = k[q];
+          *(int2*)(cell_n + 2 * idx) = nn;
+          slot_cell[s] = (int)idx;
+        }
+        ++idx;
+      }
+    }
+  }
+}
+
+// The gather pass of the product-join close over one side's log (see
+// above).  `tkeys` / `tcnt` are the retired table: found, never
+// claimed, and the side's counts of due cells counted down to zero.
+// `n*` is the fresh state.  The guards only fire if the host's
+// bookkeeping is wrong; they keep every store inside its array.
+__global__ void k_wjprod_gather(
+    const ulonglong2* __restrict__ log,
+    int64_t n,
+    int side,
+    const uint64_t* __restrict__ tkeys,
+    int* __restrict__ tcnt,
+    uint64_t mask,
+    int64_t win_lo,
+    int64_t win_hi,
+    const int* __restrict__ slot_cell,
+    const int* __restrict__ cell_n,
+    const int64_t* __restrict__ val_end,
+    int64_t ncells,
+    int64_t* __restrict__ arena,
+    int64_t arena_n,
+    uint64_t* __restrict__ nkeys,
+    int* __restrict__ ncnt,
+    ulonglong2* __restrict__ nlog,
+    int* __restrict__ nlog_n,
+    int64_t nlog_cap,
+    int* __restrict__ error_flag) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (; i < n; i += stride) {
+    const ulonglong2 e = log[i];
+    const int64_t win = (int64_t)(int32_t)(uint32_t)(e.x >> 32);
+    if (win >= win_lo && win < win_hi) {
+      uint64_t slot = lookup_slot(tkeys, mask, e.x);
+      int64_t c = slot != ~0ULL ? (int64_t)slot_cell[slot] : -1;
+      bool stored = false;
+      if (c >= 0 && c < ncells) {
+        const int n0 = cell_n[2 * c], n1 = cell_n[2 * c + 1];
+        const int pos = atomicSub(&tcnt[2 * slot + side], 1) - 1;
+        const int64_t at =
+            val_end[c] - n0 - n1 + (side ? (int64_t)n0 : 0) + pos;
+        if (pos >= 0 && pos < (side ? n1 : n0) && at >= 0 && at < arena_n) {
+          arena[at] = (int64_t)e.y;
+          stored = true;
+        }
+      }
+      if (!stored) atomicOr(error_flag, ERR_WJPROD_BOUND);
+    }
+    wjprod_put(win >= win_hi, e.x, (int64_t)e.y, nkeys, ncnt, mask, side,
+               nlog, nlog_n, nlog_cap, error_flag);
+  }
+}
+
+// The expand pass of the product-join close: one thread per output
+// row, grid-stride.  Row `r` belongs to the cell `c` with
+// row_end[c - 1] <= r < row_end[c] (an upper-bound search; a cell has
+// at least one row, so the bounds strictly increase); within it the
+// rows run over the left list in the slow index and the right list in
+// the fast one, an empty side standing for one absent value.  All row
+// arithmetic is 64-bit: one cell can pass 2^31 rows.  Consecutive rows
+// are consecutive addresses in every output column.
+__global__ void k_wjprod_expand(
+    int64_t nrows,
+    int64_t ncells,
+    const int64_t* __restrict__ row_end,
+    const int64_t* __restrict__ val_end,
+    const uint64_t* __restrict__ cell_pk,
+    const int* __restrict__ cell_n,
+    const int64_t* __restrict__ arena,
+    int32_t* __restrict__ out_keys,
+    int32_t* __restrict__ out_wins,
+    int64_t* __restrict__ out_v0,
+    int64_t* __restrict__ out_v1,
+    int32_t* __restrict__ out_mask) {
+  int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (; r < nrows; r += stride) {
+    int64_t lo = 0, hi = ncells - 1;  // row_end[ncells - 1] == nrows > r
+    while (lo < hi) {
+      int64_t mid = (lo + hi) >> 1;
+      if (row_end[mid] > r) hi = mid; else lo = mid + 1;
+    }
+    const int64_t c = lo;
+    const int64_t n0 = cell_n[2 * c], n1 = cell_n[2 * c + 1];
+    const int64_t m1 = n1 > 0 ? n1 : 1;
+    const int64_t local = r - (c > 0 ? row_end[c - 1] : 0);
+    const int64_t a = val_end[c] - n0 - n1;
+    const uint64_t pk = cell_pk[c];
+    out_keys[r] = (int32_t)(uint32_t)(pk & 0xFFFFFFFFULL);
+    out_wins[r] = (int32_t)(uint32_t)(pk >> 32);
+    out_v0[r] = n0 > 0 ? arena[a + local / m1] : 0;
+    out_v1[r] = n1 > 0 ? arena[a + n0 + local % m1] : 0;
+    out_mask[r] = (n0 > 0 ? 1 : 0) | (n1 > 0 ? 2 : 0);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Session windows (gap-based).  Per-key state is one table cell:
 // (session_start, last_ts, accumulator).  Batches arrive SORTED by
 // (key, ts) — the host wrapper sorts — and one thread walks each
@@ -7946,6 +8231,235 @@ void wjoin_pane_commit(
       error_flag.data_ptr<int32_t>());
 }
 
+// Checks of one product-join table and one side's log; returns the
+// log's capacity in entries.  `log` is int64 [2 * capacity]: 16-byte
+// entries (packed cell word, value).  `log_n` is the int32 cursor pair
+// of the two sides.
+static int64_t check_wjprod(
+    const torch::Tensor& tkeys, const torch::Tensor& tcnt,
+    const torch::Tensor& log, const torch::Tensor& log_n, int64_t side) {
+  check_dev(tkeys, torch::kInt64, "tkeys");
+  check_dev(tcnt, torch::kInt32, "tcnt");
+  check_dev(log, torch::kInt64, "log");
+  check_dev(log_n, torch::kInt32, "log_n");
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK(nslots > 0 && (nslots & (nslots - 1)) == 0,
+              "table size must be a power of two");
+  // slot_cell holds list indices below nslots as int32.
+  TORCH_CHECK(nslots <= (int64_t)1 << 30, "table too large");
+  TORCH_CHECK(tcnt.numel() == 2 * nslots, "table size mismatch");
+  TORCH_CHECK(side == 0 || side == 1, "side must be 0 or 1");
+  TORCH_CHECK(log_n.numel() == 2, "log_n must hold one cursor per side");
+  TORCH_CHECK(log.numel() % 2 == 0, "log must hold whole entries");
+  // The cursor is an int32.
+  TORCH_CHECK(log.numel() / 2 < (int64_t)INT32_MAX, "log too large");
+  TORCH_CHECK((((uintptr_t)log.data_ptr()) & 15) == 0 &&
+                  (((uintptr_t)tcnt.data_ptr()) & 7) == 0,
+              "log and counts must be 16- and 8-byte aligned");
+  return log.numel() / 2;
+}
+
+// One side's batch into the product-join table and the side's log (see
+// k_wjprod_insert): one launch.  The caller guarantees that the log
+// has room for the batch.  `ts` is absolute int64 or int32 deltas
+// against `ts_base`.
+void wjprod_insert(
+    torch::Tensor keys,
+    torch::Tensor ts,
+    torch::Tensor vals,
+    torch::Tensor tkeys,
+    torch::Tensor tcnt,
+    torch::Tensor log,
+    torch::Tensor log_n,
+    int64_t side,
+    torch::Tensor max_ts,
+    torch::Tensor error_flag,
+    int64_t align_ms,
+    int64_t len_ms,
+    int64_t ts_base) {
+  check_dev(keys, torch::kInt32, "keys");
+  check_dev(vals, torch::kInt64, "vals");
+  check_dev(max_ts, torch::kInt64, "max_ts");
+  check_dev(error_flag, torch::kInt32, "error_flag");
+  const bool ts32 = ts.scalar_type() == torch::kInt32;
+  check_dev(ts, ts32 ? torch::kInt32 : torch::kInt64, "ts");
+  int64_t log_cap = check_wjprod(tkeys, tcnt, log, log_n, side);
+  int64_t n = keys.numel();
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK(ts.numel() == n && vals.numel() == n, "column size mismatch");
+  TORCH_CHECK(len_ms > 0, "window length must be positive");
+  TORCH_CHECK(max_ts.numel() >= 1 && error_flag.numel() >= 1,
+              "max_ts and error_flag must hold one element");
+  if (n == 0) return;
+  auto stream = at::hip::getCurrentHIPStream();
+  auto run = [&](auto* tsp) {
+    using TSV = std::remove_cv_t<std::remove_pointer_t<decltype(tsp)>>;
+    hipLaunchKernelGGL(
+        k_wjprod_insert<TSV>, dim3(n_blocks(n, 256)), dim3(256), 0, stream,
+        keys.data_ptr<int32_t>(), tsp,
+        (const int64_t*)vals.data_ptr<int64_t>(), n,
+        (uint64_t*)tkeys.data_ptr<int64_t>(), tcnt.data_ptr<int32_t>(),
+        (uint64_t)(nslots - 1), (int)side,
+        (ulonglong2*)log.data_ptr<int64_t>(),
+        log_n.data_ptr<int32_t>() + side, log_cap, align_ms, len_ms, ts_base,
+        (unsigned long long*)max_ts.data_ptr<int64_t>(),
+        error_flag.data_ptr<int32_t>());
+  };
+  if (ts32)
+    run((const int32_t*)ts.data_ptr<int32_t>());
+  else
+    run((const int64_t*)ts.data_ptr<int64_t>());
+}
+
+// Plan pass of the product-join close (see k_wjprod_plan): lists the
+// cells of [win_lo, win_hi) into `cell_pk` / `cell_n` (nslots and
+// 2 * nslots long) and counts them in `cells_n`, which the caller has
+// zeroed.
+void wjprod_plan(
+    torch::Tensor tkeys,
+    torch::Tensor tcnt,
+    int64_t win_lo,
+    int64_t win_hi,
+    torch::Tensor cell_pk,
+    torch::Tensor cell_n,
+    torch::Tensor slot_cell,
+    torch::Tensor cells_n) {
+  check_dev(tkeys, torch::kInt64, "tkeys");
+  check_dev(tcnt, torch::kInt32, "tcnt");
+  check_dev(cell_pk, torch::kInt64, "cell_pk");
+  check_dev(cell_n, torch::kInt32, "cell_n");
+  check_dev(slot_cell, torch::kInt32, "slot_cell");
+  check_dev(cells_n, torch::kInt32, "cells_n");
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK(nslots > 0 && (nslots & (nslots - 1)) == 0,
+              "table size must be a power of two");
+  TORCH_CHECK(nslots <= (int64_t)1 << 30, "table too large");
+  TORCH_CHECK(tcnt.numel() == 2 * nslots && cell_pk.numel() == nslots &&
+                  cell_n.numel() == 2 * nslots &&
+                  slot_cell.numel() == nslots && cells_n.numel() >= 1,
+              "table size mismatch");
+  TORCH_CHECK((((uintptr_t)tcnt.data_ptr()) & 7) == 0 &&
+                  (((uintptr_t)cell_n.data_ptr()) & 7) == 0,
+              "counts must be 8-byte aligned");
+  int64_t nchunks = (nslots + CM_CHUNK - 1) / CM_CHUNK;
+  unsigned grid = (unsigned)(nchunks < CM_MAX_GRID ? nchunks : CM_MAX_GRID);
+  hipLaunchKernelGGL(
+      k_wjprod_plan, dim3(grid), dim3(CM_BLK), 0,
+      at::hip::getCurrentHIPStream(),
+      (const uint64_t*)tkeys.data_ptr<int64_t>(),
+      (const int*)tcnt.data_ptr<int32_t>(), nslots, win_lo, win_hi,
+      (uint64_t*)cell_pk.data_ptr<int64_t>(), cell_n.data_ptr<int32_t>(),
+      slot_cell.data_ptr<int32_t>(), cells_n.data_ptr<int32_t>());
+}
+
+// Gather pass of the product-join close over the first `n` entries of
+// one side's log (see k_wjprod_gather).  `ncells` is the plan's count,
+// `val_end` the inclusive prefix sums of n0 + n1 over its list and
+// `arena` at least val_end[ncells - 1] long.  `n*` is the fresh state:
+// an empty table, and logs with empty cursors at the call for side 0.
+void wjprod_gather(
+    torch::Tensor log,
+    int64_t n,
+    int64_t side,
+    torch::Tensor tkeys,
+    torch::Tensor tcnt,
+    torch::Tensor log_n,
+    int64_t win_lo,
+    int64_t win_hi,
+    torch::Tensor slot_cell,
+    torch::Tensor cell_n,
+    torch::Tensor val_end,
+    int64_t ncells,
+    torch::Tensor arena,
+    torch::Tensor nkeys,
+    torch::Tensor ncnt,
+    torch::Tensor nlog,
+    torch::Tensor nlog_n,
+    torch::Tensor error_flag) {
+  int64_t log_cap = check_wjprod(tkeys, tcnt, log, log_n, side);
+  int64_t nlog_cap = check_wjprod(nkeys, ncnt, nlog, nlog_n, side);
+  int64_t nslots = tkeys.numel();
+  TORCH_CHECK(nkeys.numel() == nslots, "table size mismatch");
+  check_dev(slot_cell, torch::kInt32, "slot_cell");
+  check_dev(cell_n, torch::kInt32, "cell_n");
+  check_dev(val_end, torch::kInt64, "val_end");
+  check_dev(arena, torch::kInt64, "arena");
+  check_dev(error_flag, torch::kInt32, "error_flag");
+  TORCH_CHECK(error_flag.numel() >= 1, "error_flag must hold one element");
+  TORCH_CHECK(n >= 0 && n <= log_cap, "more entries than the log holds");
+  // Every migrated entry has a place.
+  TORCH_CHECK(nlog_cap >= n, "fresh log smaller than the live entries");
+  TORCH_CHECK(ncells >= 0 && ncells <= nslots && slot_cell.numel() == nslots &&
+                  cell_n.numel() >= 2 * ncells && val_end.numel() >= ncells,
+              "plan size mismatch");
+  if (n == 0) return;
+  hipLaunchKernelGGL(
+      k_wjprod_gather, dim3(n_blocks(n, 256)), dim3(256), 0,
+      at::hip::getCurrentHIPStream(),
+      (const ulonglong2*)log.data_ptr<int64_t>(), n, (int)side,
+      (const uint64_t*)tkeys.data_ptr<int64_t>(), tcnt.data_ptr<int32_t>(),
+      (uint64_t)(nslots - 1), win_lo, win_hi,
+      (const int*)slot_cell.data_ptr<int32_t>(),
+      (const int*)cell_n.data_ptr<int32_t>(),
+      (const int64_t*)val_end.data_ptr<int64_t>(), ncells,
+      arena.data_ptr<int64_t>(), arena.numel(),
+      (uint64_t*)nkeys.data_ptr<int64_t>(), ncnt.data_ptr<int32_t>(),
+      (ulonglong2*)nlog.data_ptr<int64_t>(),
+      nlog_n.data_ptr<int32_t>() + side, nlog_cap,
+      error_flag.data_ptr<int32_t>());
+}
+
+// Expand pass of the product-join close (see k_wjprod_expand): the
+// `nrows` rows of the plan's `ncells` cells into output columns of
+// exactly that length.  `row_end` is the inclusive prefix sum of
+// max(n0, 1) * max(n1, 1) over the list, `row_end[ncells - 1] ==
+// nrows`.
+void wjprod_expand(
+    int64_t nrows,
+    int64_t ncells,
+    torch::Tensor row_end,
+    torch::Tensor val_end,
+    torch::Tensor cell_pk,
+    torch::Tensor cell_n,
+    torch::Tensor arena,
+    torch::Tensor out_keys,
+    torch::Tensor out_wins,
+    torch::Tensor out_v0,
+    torch::Tensor out_v1,
+    torch::Tensor out_mask) {
+  check_dev(row_end, torch::kInt64, "row_end");
+  check_dev(val_end, torch::kInt64, "val_end");
+  check_dev(cell_pk, torch::kInt64, "cell_pk");
+  check_dev(cell_n, torch::kInt32, "cell_n");
+  check_dev(arena, torch::kInt64, "arena");
+  check_dev(out_keys, torch::kInt32, "out_keys");
+  check_dev(out_wins, torch::kInt32, "out_wins");
+  check_dev(out_mask, torch::kInt32, "out_mask");
+  check_dev(out_v0, torch::kInt64, "out_v0");
+  check_dev(out_v1, torch::kInt64, "out_v1");
+  TORCH_CHECK(nrows >= 0 && ncells >= 0 && (nrows == 0 || ncells > 0),
+              "rows without cells");
+  TORCH_CHECK(row_end.numel() >= ncells && val_end.numel() >= ncells &&
+                  cell_pk.numel() >= ncells && cell_n.numel() >= 2 * ncells,
+              "plan size mismatch");
+  TORCH_CHECK(out_keys.numel() == nrows && out_wins.numel() == nrows &&
+                  out_mask.numel() == nrows && out_v0.numel() == nrows &&
+                  out_v1.numel() == nrows,
+              "output size mismatch");
+  if (nrows == 0) return;
+  hipLaunchKernelGGL(
+      k_wjprod_expand, dim3(n_blocks(nrows, 256)), dim3(256), 0,
+      at::hip::getCurrentHIPStream(), nrows, ncells,
+      (const int64_t*)row_end.data_ptr<int64_t>(),
+      (const int64_t*)val_end.data_ptr<int64_t>(),
+      (const uint64_t*)cell_pk.data_ptr<int64_t>(),
+      (const int*)cell_n.data_ptr<int32_t>(),
+      (const int64_t*)arena.data_ptr<int64_t>(),
+      out_keys.data_ptr<int32_t>(), out_wins.data_ptr<int32_t>(),
+      out_v0.data_ptr<int64_t>(), out_v1.data_ptr<int64_t>(),
+      out_mask.data_ptr<int32_t>());
+}
+
 int64_t filter_compact(
     torch::Tensor keys,
     torch::Tensor ts,
@@ -8878,6 +9392,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wjoin_pane_commit", &wjoin_pane_commit,
         "Sliding windowed join close, commit pass: the pane that holds a "
         "fold stamp stores its value");
+  m.def("wjprod_insert", &wjprod_insert,
+        "Windowed product join: count and append one side's batch");
+  m.def("wjprod_plan", &wjprod_plan,
+        "Windowed product join close, plan pass: list the due cells");
+  m.def("wjprod_gather", &wjprod_gather,
+        "Windowed product join close, gather pass over one side's log: "
+        "due values into the arena, live entries into the fresh state");
+  m.def("wjprod_expand", &wjprod_expand,
+        "Windowed product join close, expand pass: one row per pair");
   m.def("filter_compact", &filter_compact,
         "Stream compaction of a RecordBatch by a boolean mask");
   m.def("bucket_hist", &bucket_hist, "Per-destination counts for exchange");

@@ -41,6 +41,7 @@ __all__ = [
     "keyed_window_agg_str",
     "stream_join",
     "window_join",
+    "window_join_product",
 ]
 
 
@@ -1267,7 +1268,9 @@ def window_join(
     Raises `ValueError` at build time for an `emit_mode` other than
     ``"final"`` ("complete" and "running" depend on the order of single
     events across the sides) and for an `insert_mode` other than
-    ``"first"`` or ``"last"`` ("product" included), for an `offset`
+    ``"first"`` or ``"last"`` ("product" included: every pair of a
+    (key, window) is `window_join_product`, an operator of its own
+    over tumbling windows), for an `offset`
     that is not positive or is longer than `length`, and for more than
     64 panes per window; only two sides exist here.  Raises
     `NotImplementedError` for
@@ -1294,7 +1297,8 @@ def window_join(
     if insert_mode not in ("first", "last"):
         msg = (
             f"window_join insert mode {insert_mode!r} is not supported on "
-            "the device path: use 'first' or 'last'"
+            "the device path: use 'first' or 'last' (the product join is "
+            "its own operator, window_join_product)"
         )
         raise ValueError(msg)
     world = (
@@ -1337,6 +1341,119 @@ def window_join(
                 fold_slots_pow=fold_slots_pow,
             )
         return _DeviceWindowJoinLogic(state, wait_ms, resume_state)
+
+    shard = "shard-0"
+    l_labeled = op.map("wrap_l", left, lambda b: (shard, (0, b)))
+    r_labeled = op.map("wrap_r", right, lambda b: (shard, (1, b)))
+    merged = op.merge("merge", l_labeled, r_labeled)
+    joined = op.stateful_batch("join", merged, shim_builder)
+    return op.map("unwrap", joined, lambda kv: kv[1])
+
+
+class _DeviceWindowJoinProductLogic(_DeviceWindowJoinLogic):
+    """Holds the HBM product-join table and logs; values are (side,
+    RecordBatch).  Batches, closes, EOF and the ``__world__`` tag of a
+    snapshot are handled as `_DeviceWindowJoinLogic` handles them: the
+    two states share that surface."""
+
+
+@operator
+def window_join_product(
+    step_id: str,
+    left: Stream[RecordBatch],
+    right: Stream[RecordBatch],
+    align_to: datetime,
+    length: timedelta,
+    wait: timedelta = timedelta(0),
+    slots_pow: int = 20,
+    out_cap: int = 1 << 20,
+    log_cap: int = 1 << 20,
+    device: str = "cuda",
+    exchange: Optional[bool] = None,
+) -> Stream[Dict[str, Any]]:
+    """Two-sided product join over tumbling event-time windows of
+    columnar batches on GPU: within each window, every left event of a
+    key paired with every right event of that key.  The device
+    counterpart of `join_window` with an `EventClock`, a
+    `TumblingWindower`, ``insert_mode="product"``,
+    ``emit_mode="final"`` and ``ordered=True``.
+
+    An event ``(key, ts, val)`` of either side belongs to window
+    ``(ts - align_to) // length``, and each (key, window) cell keeps
+    every value of each side, duplicates included.  Once the watermark
+    minus `wait` passes a window's end, each of its cells is emitted
+    once, as the rows of the product of its two value lists; an empty
+    side counts as one absent value, so a cell with n0 left and n1
+    right values gives ``max(n0, 1) * max(n1, 1)`` rows.  The output is
+    a dict of columnar device tensors {keys, wins, v0, v1, mask}, the
+    names and dtypes `window_join` emits: ``mask`` bit 0 says the left
+    side is present, bit 1 the right, and an absent side's value column
+    reads 0 (values are arbitrary int64, so only the mask tells).  At
+    EOF every remaining cell is emitted.
+
+    Row order is not defined, within a cell or across cells, and may
+    differ from run to run: what is guaranteed is the multiset of
+    ``(key, win, v0-or-absent, v1-or-absent)``, which equals the host
+    operator's exactly.  All rows of a cell come out of one close, and
+    no cell comes out twice.
+
+    A close reclaims what it emits, so the stream may run unbounded.
+    Size `slots_pow` (2^slots_pow table slots, best kept under half
+    full) for the (key, window) cells open at one time, and `out_cap`
+    for the rows of one close: the row count of a cell is a product, a
+    hot key can make it large, and a close with more rows raises
+    rather than emit part of it.  `log_cap` is the initial capacity of
+    each side's event log, in events; the logs grow by doubling as the
+    open windows need, so it is a starting point, not a limit.
+
+    The ordering contract is `window_join`'s: ingestion must be
+    watermark-ordered across batches, this operator does not track
+    late events and nothing checks the ordering; an event behind the
+    closed horizon is dropped by a later close.  No event may lie
+    before `align_to`, and window ids lie within int32.  Timestamps
+    are absolute int64 or int32 deltas against ``ts_base``; they only
+    choose the window and move the watermark.
+
+    Raises `ValueError` at build time for a `length` that is not
+    positive and `NotImplementedError` for ``exchange=True`` or a
+    process group of more than one rank.  Raises `RuntimeError` when
+    the table overflows (increase `slots_pow`) or when one close has
+    more than `out_cap` rows; the message carries the exact row count,
+    nothing has been emitted or reclaimed at that point, and neither
+    error ever returns short output.
+    """
+    import torch
+    import torch.distributed as dist
+
+    from .state import WindowJoinProductState
+    from . import _ms as to_ms
+
+    world = (
+        dist.get_world_size()
+        if dist.is_available() and dist.is_initialized()
+        else 1
+    )
+    if exchange or world > 1:
+        msg = (
+            "window_join_product is single-GPU: a multi-GPU windowed join "
+            "needs the two sides' collectives ordered identically on every "
+            "rank, which this operator does not do yet"
+        )
+        raise NotImplementedError(msg)
+
+    align_ms = to_ms(align_to)
+    len_ms = int(length.total_seconds() * 1000)
+    wait_ms = int(wait.total_seconds() * 1000)
+    if len_ms <= 0:
+        msg = "window_join_product length must be positive"
+        raise ValueError(msg)
+
+    def shim_builder(resume_state):
+        state = WindowJoinProductState(
+            torch.device(device), align_ms, len_ms, slots_pow=slots_pow,
+            out_cap=out_cap, wait_ms=wait_ms, log_cap=log_cap,
+        )
+        return _DeviceWindowJoinProductLogic(state, wait_ms, resume_state)
 
     shard = "shard-0"
     l_labeled = op.map("wrap_l", left, lambda b: (shard, (0, b)))

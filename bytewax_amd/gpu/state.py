@@ -11,7 +11,9 @@ Device twins of `reduce_final`-style keyed aggregations and the
   window, "first" or "last" insert / "final" emit, with a close that
   reclaims the closed cells;
 - :class:`SlidingWindowJoinState` — that join over sliding windows:
-  one insert per event into panes, folded per window at close.
+  one insert per event into panes, folded per window at close;
+- :class:`WindowJoinProductState` — the tumbling windowed join with
+  "product" insert: every left value of a cell with every right one.
 
 All support pinned-host snapshot spill for recovery and have CPU
 twins for GPU-less test runs.
@@ -1207,6 +1209,8 @@ class HashJoinState:
 
 _WJOIN_COLS = ("keys", "wins", "v0", "v1", "mask")
 _WJOIN_MODES = ("first", "last")
+#: Kind tag of a `WindowJoinProductState` snapshot.
+_WJPROD_KIND = "window_join_product"
 
 
 def _wjoin_rows(hit) -> Optional[Dict[str, Any]]:
@@ -1662,6 +1666,12 @@ class WindowJoinState:
         taken without restores into either kind."""
         import torch
 
+        if snap.get("kind") == _WJPROD_KIND:
+            msg = (
+                "snapshot of a window product join holds value lists and "
+                "cannot restore a 'first' / 'last' window join"
+            )
+            raise ValueError(msg)
         self._check_kind(snap)
         theirs = (
             snap.get("align_ms"), snap.get("len_ms"), snap.get("insert_mode")
@@ -2014,6 +2024,491 @@ class SlidingWindowJoinState(WindowJoinState):
         tumbling join, is refused."""
         super().restore_from_host(snap)
         self.win_horizon = snap["win_horizon"]
+
+
+#: Error-flag bit of the product join's device guards (a log, arena or
+#: segment position out of range): the host's bookkeeping is wrong.
+_ERR_WJPROD_BOUND = 4
+
+
+class WindowJoinProductState:
+    """Two-sided join over tumbling event-time windows on device with
+    "product" insert and "final" emit: the device twin of the host
+    `join_window` with an `EventClock`, a `TumblingWindower`,
+    ``insert_mode="product"`` and ``ordered=True``.
+
+    Each (key, window) cell keeps every value of each side, duplicates
+    included.  A close emits each cell of a due window once, as the
+    rows of the product of its two value lists, an empty side counting
+    as one absent value: a cell with n0 left and n1 right values gives
+    ``max(n0, 1) * max(n1, 1)`` rows of the columns `keys`, `wins`,
+    `v0`, `v1` and `mask` (bit ``s`` set: side ``s`` present; an absent
+    side's value column reads 0).  All rows of a cell come out of one
+    close.  The order of the rows is not defined, within a cell or
+    across cells, and may differ from run to run: the contract is the
+    multiset of ``(key, win, v0-or-absent, v1-or-absent)``.
+
+    On device the state is a (window << 32 | key) table with a count
+    per side and slot, and one append log per side of (cell, value)
+    entries.  A close plans the due cells, gathers their values from
+    the logs into an arena while it compacts the live entries into a
+    fresh table and fresh logs, and expands the arena into rows (see
+    k_wjprod_plan, k_wjprod_gather and k_wjprod_expand).  So table and
+    logs only ever hold the open windows.  `log_cap` is the initial
+    capacity of each side's log in entries; a log grows by doubling
+    before an insert that could pass it, from a host-side bound on the
+    live entries (`live_counts`), so it never overflows.
+
+    The ordering contract is `WindowJoinState`'s without late
+    tracking: nothing checks the order, and an event behind the closed
+    horizon is dropped by the next close that has rows.  Timestamps
+    only choose the window and move the watermark.
+
+    A close whose row total exceeds `out_cap` raises `RuntimeError`
+    with the exact total before anything is emitted or reclaimed: the
+    state then holds what it held before.
+    """
+
+    def __init__(
+        self,
+        device,
+        align_ms: int,
+        len_ms: int,
+        slots_pow: int = 20,
+        out_cap: int = 1 << 20,
+        wait_ms: int = 0,
+        log_cap: int = 1 << 20,
+    ):
+        import torch
+
+        if len_ms <= 0:
+            msg = "window length must be positive"
+            raise ValueError(msg)
+        self.device = device
+        self.align_ms = align_ms
+        self.len_ms = len_ms
+        self.wait_ms = wait_ms
+        self.out_cap = out_cap
+        self.max_ts_host = 0
+        self.closed_horizon = -(1 << 62)
+        self._log_caps = [max(1, log_cap)] * 2
+        self.cpu = device.type == "cpu"
+        if self.cpu:
+            #: (key, win) -> [left values, right values].
+            self._table: Dict[Tuple[int, int], List[List[int]]] = {}
+            return
+        self.k = ext()
+        self.nslots = 1 << slots_pow
+        self.tkeys, self.tcnt = self._new_table()
+        #: The second table and logs that a close rebuilds the live
+        #: entries into.  None until a close has rows to emit.
+        self.table_alt: Optional[Tuple[Any, Any]] = None
+        self.logs = [self._new_log(side) for side in (0, 1)]
+        self.logs_alt: List[Any] = [None, None]
+        #: Device cursors of the two logs: entries appended so far.
+        self.log_n = torch.zeros(2, dtype=torch.int32, device=device)
+        self.log_n_alt = torch.zeros(2, dtype=torch.int32, device=device)
+        #: Upper bound on each log's entries: the cursor read back at
+        #: the last close, less what that close took, plus the batch
+        #: lengths inserted since.
+        self._live = [0, 0]
+        #: The plan's due-cell list and per-slot scratch, allocated by
+        #: the first close.
+        self._plan: Optional[Tuple[Any, Any, Any]] = None
+        self.cells_n = torch.zeros(1, dtype=torch.int32, device=device)
+        self.max_ts_dev = torch.zeros(1, dtype=torch.int64, device=device)
+        self.error_flag = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def _new_table(self) -> Tuple[Any, Any]:
+        import torch
+
+        return (
+            torch.full(
+                (self.nslots,), -1, dtype=torch.int64, device=self.device
+            ),
+            torch.zeros(2 * self.nslots, dtype=torch.int32, device=self.device),
+        )
+
+    def _new_log(self, side: int):
+        import torch
+
+        return torch.empty(
+            2 * self._log_caps[side], dtype=torch.int64, device=self.device
+        )
+
+    @property
+    def log_caps(self) -> Tuple[int, int]:
+        """Current capacity of each side's log, in entries."""
+        return (self._log_caps[0], self._log_caps[1])
+
+    @property
+    def live_counts(self) -> Tuple[int, int]:
+        """Entries each side holds.  On device this is the host's
+        bound, without a synchronisation: exact unless the last close
+        dropped events behind the closed horizon, and never too low."""
+        if self.cpu:
+            return (
+                sum(len(c[0]) for c in self._table.values()),
+                sum(len(c[1]) for c in self._table.values()),
+            )
+        return (self._live[0], self._live[1])
+
+    def _reserve(self, side: int, n: int) -> None:
+        """Room for `n` more entries in the side's log: grow it by
+        doubling, copying the live prefix on the stream."""
+        need = self._live[side] + n
+        cap = self._log_caps[side]
+        if need <= cap:
+            return
+        while cap < need:
+            cap *= 2
+        old = self.logs[side]
+        self._log_caps[side] = cap
+        self.logs[side] = self._new_log(side)
+        live = 2 * self._live[side]
+        self.logs[side][:live].copy_(old[:live])
+        # The spare log is empty between closes: the next close makes
+        # one of the new size.
+        self.logs_alt[side] = None
+
+    def insert(self, side: int, batch: RecordBatch) -> None:
+        """Insert one side's batch (`side` 0 = left, 1 = right)."""
+        if side not in (0, 1):
+            msg = f"window join side must be 0 or 1, not {side!r}"
+            raise ValueError(msg)
+        if batch.vals is None:
+            msg = "window join requires a `vals` column"
+            raise ValueError(msg)
+        n = len(batch)
+        if self.cpu:
+            self._insert_cpu(side, batch)
+            return
+        if n:
+            self._reserve(side, n)
+            self.k.wjprod_insert(
+                batch.keys,
+                batch.ts,
+                batch.vals,
+                self.tkeys,
+                self.tcnt,
+                self.logs[side],
+                self.log_n,
+                side,
+                self.max_ts_dev,
+                self.error_flag,
+                self.align_ms,
+                self.len_ms,
+                batch.ts_base,
+            )
+            self._live[side] += n
+        if batch.max_ts is not None:
+            if batch.max_ts > self.max_ts_host:
+                self.max_ts_host = batch.max_ts
+        elif n:
+            # No host-side hint: the watermark has to come back from
+            # the device.
+            dev_max = int(self.max_ts_dev.item())
+            if dev_max > self.max_ts_host:
+                self.max_ts_host = dev_max
+
+    def _insert_cpu(self, side: int, batch: RecordBatch) -> None:
+        import torch
+
+        keys = batch.keys.tolist()
+        ts = (batch.ts.to(torch.int64) + batch.ts_base).tolist()
+        vals = batch.vals.tolist()
+        for k, t, v in zip(keys, ts, vals):
+            kw = (k, (t - self.align_ms) // self.len_ms)
+            cell = self._table.get(kw)
+            if cell is None:
+                cell = self._table[kw] = [[], []]
+            cell[side].append(v)
+        mx_ts = batch.max_ts
+        if mx_ts is None and ts:
+            mx_ts = max(ts)
+        if mx_ts is not None and mx_ts > self.max_ts_host:
+            self.max_ts_host = mx_ts
+
+    def _win_lo(self) -> int:
+        return max(self.closed_horizon, -(1 << 39))
+
+    def _too_many(self, rows: int) -> None:
+        if rows > self.out_cap:
+            msg = (
+                f"window product join close has {rows} rows > out_cap "
+                f"{self.out_cap}; nothing was emitted or reclaimed"
+            )
+            raise RuntimeError(msg)
+
+    def close_due(
+        self, wait_ms: Optional[int] = None
+    ) -> Optional[Dict[str, Any]]:
+        """Emit every window fully below the watermark (`max_ts_host`
+        minus `wait_ms`, the constructor's by default) and reclaim its
+        space; None when nothing was due.  See :meth:`close_below`."""
+        return self.close_below(self.horizon_for(self.max_ts_host, wait_ms))
+
+    def horizon_for(
+        self, watermark_ms: int, wait_ms: Optional[int] = None
+    ) -> int:
+        """The window horizon of a watermark: every window below it
+        ends at or before `watermark_ms` minus `wait_ms` (the
+        constructor's by default).  What :meth:`close_below` takes."""
+        if wait_ms is None:
+            wait_ms = self.wait_ms
+        return (watermark_ms - wait_ms - self.align_ms) // self.len_ms
+
+    def close_eof(self) -> Optional[Dict[str, Any]]:
+        """End of input, as the operator closes it: the rows of every
+        cell at or above the closed horizon, with the horizon left
+        where it is and the state left empty."""
+        return self._close(self._win_lo(), 1 << 40)
+
+    def close_all(self) -> Optional[Dict[str, Any]]:
+        """EOF: the rows of every cell at or above the closed horizon;
+        the state is left empty and nothing is emitted after it."""
+        out = self._close(self._win_lo(), 1 << 40)
+        self.closed_horizon = 1 << 40
+        return out
+
+    def close_below(self, horizon: int) -> Optional[Dict[str, Any]]:
+        """Close with reclamation: return the rows of the cells of
+        windows in [closed_horizon, horizon), each cell exactly once
+        and whole, keep the events at or above `horizon`, forget
+        everything below it and advance `closed_horizon` to `horizon`.
+        An event below `closed_horizon` (one behind the watermark) was
+        never going to be emitted; it is dropped here, on device by
+        the next close that has rows."""
+        if horizon <= self.closed_horizon:
+            return None
+        out = self._close(self._win_lo(), min(horizon, 1 << 40))
+        self.closed_horizon = horizon
+        return out
+
+    def _close(self, win_lo: int, win_hi: int) -> Optional[Dict[str, Any]]:
+        import torch
+
+        if self.cpu:
+            return self._close_cpu(win_lo, win_hi)
+        if self._plan is None:
+            self._plan = (
+                torch.empty(self.nslots, dtype=torch.int64, device=self.device),
+                torch.empty(
+                    2 * self.nslots, dtype=torch.int32, device=self.device
+                ),
+                torch.empty(self.nslots, dtype=torch.int32, device=self.device),
+            )
+        cell_pk, cell_n, slot_cell = self._plan
+        self.cells_n.zero_()
+        self.k.wjprod_plan(
+            self.tkeys, self.tcnt, win_lo, win_hi,
+            cell_pk, cell_n, slot_cell, self.cells_n,
+        )
+        # A cell holds at least one entry, so the list is no longer
+        # than the host's bound on the entries; rows past the list's
+        # end hold earlier closes' cells and count for nothing.
+        ub = max(1, min(self.nslots, self._live[0] + self._live[1]))
+        nn = cell_n[: 2 * ub].view(ub, 2).to(torch.int64)
+        listed = (
+            torch.arange(ub, device=self.device) < self.cells_n
+        ).to(torch.int64)
+        n0, n1 = nn[:, 0] * listed, nn[:, 1] * listed
+        val_end = torch.cumsum(n0 + n1, 0)
+        row_end = torch.cumsum(
+            n0.clamp(min=1) * n1.clamp(min=1) * listed, 0
+        )
+        # The one readback of a close: list length, row and value
+        # totals, the error flag and both log cursors.
+        ncells, rows, nvals, due0, flag, cur0, cur1 = torch.cat(
+            [
+                self.cells_n.to(torch.int64),
+                row_end[-1:],
+                val_end[-1:],
+                n0.sum().reshape(1),
+                self.error_flag.to(torch.int64),
+                self.log_n.to(torch.int64),
+            ]
+        ).tolist()
+        if flag & _ERR_WJPROD_BOUND:
+            msg = (
+                "window product join wrote past a log or arena bound on "
+                "device; this is a bug in the host-side bound"
+            )
+            raise RuntimeError(msg)
+        _check_error_flag(flag, "window product join table")
+        if ncells > ub:
+            msg = "window product join: more due cells than live entries"
+            raise RuntimeError(msg)
+        self._too_many(rows)
+        self._live = [cur0, cur1]
+        if ncells == 0:
+            # Nothing due, so nothing to reclaim yet.
+            return None
+        if self.table_alt is None:
+            self.table_alt = self._new_table()
+        for side in (0, 1):
+            if self.logs_alt[side] is None:
+                self.logs_alt[side] = self._new_log(side)
+        arena = torch.empty(nvals, dtype=torch.int64, device=self.device)
+        for side, cur in ((0, cur0), (1, cur1)):
+            self.k.wjprod_gather(
+                self.logs[side], cur, side, self.tkeys, self.tcnt,
+                self.log_n, win_lo, win_hi, slot_cell, cell_n, val_end,
+                ncells, arena, *self.table_alt, self.logs_alt[side],
+                self.log_n_alt, self.error_flag,
+            )
+        out = {
+            name: torch.empty(
+                rows,
+                dtype=torch.int64 if name[0] == "v" else torch.int32,
+                device=self.device,
+            )
+            for name in _WJOIN_COLS
+        }
+        self.k.wjprod_expand(
+            rows, ncells, row_end, val_end, cell_pk, cell_n, arena,
+            *(out[c] for c in _WJOIN_COLS),
+        )
+        retired = (self.tkeys, self.tcnt)
+        self.tkeys, self.tcnt = self.table_alt
+        self.table_alt = retired
+        self.logs, self.logs_alt = self.logs_alt, self.logs
+        self.log_n, self.log_n_alt = self.log_n_alt, self.log_n
+        # Reset the retired table and cursors on the stream for the
+        # next close; the retired logs need none.
+        retired[0].fill_(-1)
+        retired[1].zero_()
+        self.log_n_alt.zero_()
+        self._live = [cur0 - due0, cur1 - (nvals - due0)]
+        return out
+
+    def _close_cpu(self, win_lo: int, win_hi: int) -> Optional[Dict[str, Any]]:
+        import torch
+
+        hit = [
+            (k, w, c)
+            for (k, w), c in self._table.items()
+            if win_lo <= w < win_hi
+        ]
+        self._too_many(
+            sum(max(len(c[0]), 1) * max(len(c[1]), 1) for *_x, c in hit)
+        )
+        for kw in [kw for kw in self._table if kw[1] < win_hi]:
+            del self._table[kw]
+        if not hit:
+            return None
+        rows = [
+            (k, w, a, b)
+            for k, w, c in hit
+            for a in (c[0] or [None])
+            for b in (c[1] or [None])
+        ]
+        return {
+            "keys": torch.tensor([r[0] for r in rows], dtype=torch.int32),
+            "wins": torch.tensor([r[1] for r in rows], dtype=torch.int32),
+            "v0": torch.tensor(
+                [0 if r[2] is None else r[2] for r in rows], dtype=torch.int64
+            ),
+            "v1": torch.tensor(
+                [0 if r[3] is None else r[3] for r in rows], dtype=torch.int64
+            ),
+            "mask": torch.tensor(
+                [(r[2] is not None) | ((r[3] is not None) << 1) for r in rows],
+                dtype=torch.int32,
+            ),
+        }
+
+    def snapshot_to_host(self) -> Dict[str, Any]:
+        """Spill the live events of windows at or above the closed
+        horizon as columns `keys`, `wins`, `sides` and `vals`, with
+        the watermark, the closed horizon, the window geometry and a
+        kind tag.  Nothing on the device is changed."""
+        import numpy as np
+
+        if self.cpu:
+            ev = [
+                (k, w, side, v)
+                for (k, w), c in self._table.items()
+                if w >= self.closed_horizon
+                for side in (0, 1)
+                for v in c[side]
+            ]
+            cols = [
+                np.array([e[j] for e in ev], dtype=dt)
+                for j, dt in enumerate((np.int32, np.int32, np.int32, np.int64))
+            ]
+        else:
+            cur = self.log_n.tolist()
+            _check_error_flag(
+                int(self.error_flag.item()), "window product join table"
+            )
+            parts = []
+            for side in (0, 1):
+                log = self.logs[side][: 2 * cur[side]].cpu().numpy()
+                packed, vals = log[0::2], log[1::2]
+                wins = (packed >> 32).astype(np.int32)
+                keys = (packed & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+                live = wins.astype(np.int64) >= self.closed_horizon
+                parts.append(
+                    (
+                        keys[live],
+                        wins[live],
+                        np.full(int(live.sum()), side, dtype=np.int32),
+                        vals[live].copy(),
+                    )
+                )
+            cols = [np.concatenate(c) for c in zip(*parts)]
+        return {
+            "kind": _WJPROD_KIND,
+            "max_ts": self.max_ts_host,
+            "closed_horizon": self.closed_horizon,
+            "align_ms": self.align_ms,
+            "len_ms": self.len_ms,
+            "n": len(cols[0]),
+            "keys": cols[0],
+            "wins": cols[1],
+            "sides": cols[2],
+            "vals": cols[3],
+        }
+
+    def restore_from_host(self, snap: Dict[str, Any]) -> None:
+        """Re-insert the live events, each at the start of its window:
+        the timestamp of an event only ever chose its window.  A
+        snapshot of another geometry, or of a "first" / "last" or
+        sliding window join, is refused."""
+        import torch
+
+        if snap.get("kind") != _WJPROD_KIND:
+            msg = (
+                "snapshot of another kind of window join cannot restore a "
+                "window product join"
+            )
+            raise ValueError(msg)
+        theirs = (snap.get("align_ms"), snap.get("len_ms"))
+        mine = (self.align_ms, self.len_ms)
+        if theirs != mine:
+            msg = (
+                "snapshot of a window product join with (align_ms, len_ms) "
+                f"= {theirs} cannot restore one with {mine}"
+            )
+            raise ValueError(msg)
+        if snap["n"]:
+            for side in (0, 1):
+                m = snap["sides"] == side
+                if not m.any():
+                    continue
+                ts = self.align_ms + snap["wins"][m].astype("int64") * self.len_ms
+                self.insert(
+                    side,
+                    RecordBatch(
+                        torch.as_tensor(snap["keys"][m]).to(self.device),
+                        torch.as_tensor(ts).to(self.device),
+                        torch.as_tensor(snap["vals"][m]).to(self.device),
+                        max_ts=snap["max_ts"],
+                    ),
+                )
+        self.max_ts_host = snap["max_ts"]
+        self.closed_horizon = snap["closed_horizon"]
 
 
 class SessionAggState:
